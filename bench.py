@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — decode tok/s of the `hip` attention backend in a bench_my.py-shaped run (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: engine start-up, prefill, W untimed and K timed decode
+steps, the result line.  --dump-outputs DIR then writes what the timed steps computed (see timed_outputs) as DIR/<name>.npy;
+the inputs are seeded, so two builds can be compared output for output.  --full adds every other measurement listed below.
 
 Workload (BASELINE.json configs[1]): Qwen2-0.5B shapes, random-init bf16 weights, bs=32 sequences of
 1024 random prompt tokens (`random.seed(0)`, `randint(0, 10000)`, bench_my.py:27-40), greedy decode with
@@ -13,7 +17,8 @@ body around it, replayed from a HIP graph with device-resident metadata.  Prefil
 region (it is reported separately, and the bench_my-style figure that includes it is in `bench_my_tok_s`).
 The K timed steps start at context 1025 as bench_my's decode phase does (K = 1024 covers 1025 -> 2048).
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Output: ONE JSON line on rank 0 (metric, value, unit, ms_per_step, the workload's config, prefill_s, bench_my_tok_s), and
+with --full these extra objects:
   roofline      the decode attention op (nvh_paged_decode: one chunked split-KV launch, combine included) at the mean context of the
                 timed window, timed live with HIP events on the launching stream over a graph of per-layer calls
                 on distinct caches; achieved = algorithmic bytes / average time per call; traffic = HBM bytes per call from the
@@ -291,6 +296,28 @@ def cpu_baseline_leg(cfg, batch, ctx, budget_s=10.0):
                         "cores": torch.get_num_threads(), "kind": "port"}}
 
 
+DUMP_TOKEN_BYTES = 4 << 20        # --dump-outputs: the token log keeps its last steps up to this size,
+DUMP_KV_BYTES = 56 << 20          # the appended K / V rows a seeded sample of the batch up to this one (64 MB in all at most)
+
+
+def timed_outputs(engine, sess, steps):
+    """What the timed decode steps handed to their caller, as float arrays: `tokens` [steps, batch] = the greedy token of every
+    sequence at every timed step (the session's token log, which DecodeSession.finish() returns), and `kv_last_step`
+    [2, layers, batch, kv heads of this rank, head_dim] = the K and V rows that the LAST timed step appended to every layer's
+    cache, the floating-point result of a step that outlives it (the next step's attention reads them)."""
+    batch, bs = sess.batch, engine.runner.block_size
+    keep = max(1, min(steps, DUMP_TOKEN_BYTES // (8 * batch)))
+    tokens = sess.tokens[steps - keep:steps].double().cpu().numpy()
+    pos = (sess.context_lens - 2).long()                                 # context_lens - 1 is the slot the NEXT step fills
+    blk = torch.gather(sess.block_tables, 1, (pos // bs).unsqueeze(1)).squeeze(1).long()
+    slots = blk * bs + pos % bs
+    kv = engine.runner.kv_cache                                          # [2, layers, blocks, block_size, kv heads, head_dim]
+    rows = max(1, min(batch, DUMP_KV_BYTES // (4 * kv[:, :, 0, 0].numel())))
+    if rows < batch:
+        slots = slots[torch.randperm(batch, generator=torch.Generator().manual_seed(0))[:rows].sort().values.to(slots.device)]
+    return {"tokens": tokens, "kv_last_step": kv.flatten(2, 3)[:, :, slots].float().cpu().numpy()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -299,6 +326,11 @@ def main():
     ap.add_argument("--model", default="Qwen2-0.5B")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--input-len", type=int, default=1024)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (timed_outputs) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the attention and prefill roofline legs, PMC traffic, the "
+                         "step floor, bench_my's whole decode window, the attention sweep and the CPU baseline (the --no-* options trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager", action="store_true", help="no HIP graph (debug)")
     ap.add_argument("--graph-steps", type=int, default=0, help="A/B: decode steps captured per replayed graph (0 = the session's default)")
@@ -356,7 +388,8 @@ def main():
         _qwen.KV_PREFETCH_PASSES = args.kv_prefetch_passes
     cfg = model_config(args.model)
     bs = cfg.kvcache_block_size
-    window = max(args.steps, args.input_len) if not args.no_full_window else args.steps      # bench_my's decode phase: out = in tokens
+    # bench_my's decode phase: out = in tokens (reserved by the sequences of a plain run too: the same block tables and graphs as under --full)
+    window = max(args.steps, args.input_len) if not args.no_full_window else args.steps
     total_len = args.input_len + window + args.warmup + 2
     blocks_per_seq = (total_len + bs - 1) // bs
     def run_decode():
@@ -401,10 +434,14 @@ def main():
             elapsed = float(t.item())
         tok_s = args.batch * args.steps / elapsed
         engine.runner.raise_if_device_failed()
+        if args.dump_outputs and rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in timed_outputs(engine, sess, args.steps).items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
         # ---- the whole bench_my window (contexts in+1 -> 2 in), once more from the same start: what bench_my.py:27-40 reports for in = out
         full = None
-        if not args.no_full_window:
+        if args.full and not args.no_full_window:
             if window == args.steps:
                 full_elapsed = elapsed
             else:
@@ -440,22 +477,23 @@ def main():
         engine, seqs, prefill_s, ctx0, sess, elapsed, graph_mode, full = run_decode()
     tok_s = args.batch * args.steps / elapsed
 
-    # ---- roofline leg: the attention op alone at the mean context of the timed window
     mean_ctx = ctx0 + (args.steps - 1) // 2
     tp = world
-    attn_us, attn_bytes, shape_rank = attention_leg(cfg, tp, args.batch, mean_ctx, cfg.num_hidden_layers)
-    achieved = attn_bytes / attn_us / 1e3                              # GB/s
+    if args.full:
+        # ---- roofline leg: the attention op alone at the mean context of the timed window
+        attn_us, attn_bytes, shape_rank = attention_leg(cfg, tp, args.batch, mean_ctx, cfg.num_hidden_layers)
+        achieved = attn_bytes / attn_us / 1e3                              # GB/s
 
-    traffic, traffic_note = pmc_traffic(cfg, tp, args.batch, mean_ctx, attn_bytes)
-    prefill = None
-    if args.model == "Qwen2-0.5B" or args.prefill_leg:
-        del sess
-        torch.cuda.empty_cache()
-        prefill = {"config5_half": prefill_leg(cfg, tp, 128, 128), "s1024": prefill_leg(cfg, tp, 16, 1024, buffers=8, iters=4),
-                   "s1024_exact_hi_lo": prefill_leg(cfg, tp, 16, 1024, buffers=8, iters=4, pv_fp16=False)}
-    sweep = None
-    if args.model == "Qwen2-0.5B" and world == 1 and not args.no_sweep:
-        sweep = attention_sweep(cfg)
+        traffic, traffic_note = pmc_traffic(cfg, tp, args.batch, mean_ctx, attn_bytes)
+        prefill = None
+        if args.model == "Qwen2-0.5B" or args.prefill_leg:
+            del sess
+            torch.cuda.empty_cache()
+            prefill = {"config5_half": prefill_leg(cfg, tp, 128, 128), "s1024": prefill_leg(cfg, tp, 16, 1024, buffers=8, iters=4),
+                       "s1024_exact_hi_lo": prefill_leg(cfg, tp, 16, 1024, buffers=8, iters=4, pv_fp16=False)}
+        sweep = None
+        if args.model == "Qwen2-0.5B" and world == 1 and not args.no_sweep:
+            sweep = attention_sweep(cfg)
     from nanovllm_hip import distributed as nvh_dist
     tp_choice = nvh_dist.last_choice
     failed_epoch = engine.runner.comm.failed_epoch() if engine.runner.comm is not None else None
@@ -464,12 +502,6 @@ def main():
 
     result = None
     if rank == 0:
-        weight_bytes = sum(p.numel() * p.element_size() for p in engine.runner.model.parameters())
-        step_bytes = weight_bytes + cfg.num_hidden_layers * attn_bytes
-        step_us = elapsed / args.steps * 1e6
-        layers = cfg.num_hidden_layers
-        attn_floor_us = ATTN_FIXED_FLOOR_US + attn_bytes / (HBM_SUSTAINED_GBPS * 1e3)
-        step_floor_us = step_us - layers * max(attn_us - attn_floor_us, 0.0)
         result = {
             "metric": "decode tok/s (bench_my.py) Qwen2-0.5B bs=32 in=out=1024; % HBM roofline" if args.model == "Qwen2-0.5B" and args.batch == 32
                       else f"decode tok/s (bench_my.py-shaped) {args.model} bs={args.batch}",
@@ -486,6 +518,17 @@ def main():
                                               "startup_measurement_us": nvh_dist.last_measurement, "failed_epoch": failed_epoch,
                                               "note": oneshot_note} if world > 1 else None),
                        "heads_per_rank_q0_qn_kv0_kvn": shapes},
+            "prefill_s": round(prefill_s, 4),
+            "bench_my_tok_s": round(args.batch * (args.steps + 1) / (prefill_s + elapsed), 1),
+        }
+    if rank == 0 and args.full:
+        weight_bytes = sum(p.numel() * p.element_size() for p in engine.runner.model.parameters())
+        step_bytes = weight_bytes + cfg.num_hidden_layers * attn_bytes
+        step_us = elapsed / args.steps * 1e6
+        layers = cfg.num_hidden_layers
+        attn_floor_us = ATTN_FIXED_FLOOR_US + attn_bytes / (HBM_SUSTAINED_GBPS * 1e3)
+        step_floor_us = step_us - layers * max(attn_us - attn_floor_us, 0.0)
+        result.update({
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_note,
                          "kernel": "one decode attention call (nvh_paged_decode) = one launch of paged_decode_chunked_kernel (split-KV passes + last-arriver combine)",
@@ -507,15 +550,14 @@ def main():
                              "bench_my_tok_s": round(args.batch * (full[0] + 1) / (prefill_s + full[1]), 1)} if full else None),
             "attention_sweep": sweep,
             "prefill": prefill,
-            "prefill_s": round(prefill_s, 4),
-            "bench_my_tok_s": round(args.batch * (args.steps + 1) / (prefill_s + elapsed), 1),
             "attention_only_tok_s": round(args.batch / (attn_us * 1e-6 * cfg.num_hidden_layers), 1),
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, ROOT)
             result["cpu_baseline"] = cpu_baseline_leg(cfg, args.batch, mean_ctx)
         else:
             result["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

@@ -52,6 +52,9 @@ def _model_out(cfg_kwargs, lens):
 
 
 def _worker(rank, world, port, cfg_kwargs, lens, ret):
+    # a CPU rank also where the suite runs beside a GPU: hide the devices from this process before anything asks for them
+    os.environ["HIP_VISIBLE_DEVICES"] = os.environ["CUDA_VISIBLE_DEVICES"] = "-1"
+    assert not torch.cuda.is_available()
     for p in (ROOT, os.path.join(ROOT, "nano-vllm-learn_amd")):
         if p not in sys.path:
             sys.path.insert(0, p)

@@ -8,7 +8,7 @@ for round in 1 2; do
   for v in "$@"; do
     if [ "$v" = "-" ]; then unset $var; else export $var=$v; fi
     err=gpurun_out/env/${var}_${v}_round${round}.stderr
-    out=$(timeout -k 10 300 python bench.py --steps 256 --no-cpu-baseline 2>"$err"); rc=$?
+    out=$(timeout -k 10 300 python bench.py --full --steps 256 --no-cpu-baseline 2>"$err"); rc=$?
     line=$(printf '%s\n' "$out" | python3 -c "import sys,json
 ls=[l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')]
 d=json.loads(ls[-1]) if ls else None

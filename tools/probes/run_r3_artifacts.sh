@@ -7,8 +7,9 @@ cd $GRAFT_REPO_ROOT
 bash tools/probes/run_pmc_traffic.sh || { echo "pmc traffic failed"; exit 1; }
 cp gpurun_out/r03_pmc_decode_traffic.json profiles/ 2>/dev/null
 echo "[progress] pmc traffic done"
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_steps20.log 2>gpurun_out/bench_steps20.err || { tail -5 gpurun_out/bench_steps20.err; exit 1; }
-tail -1 gpurun_out/bench_steps20.log > gpurun_out/r03_bench_steps20_line.json
+O=${NVH_PROBE_OUT:-probe_out}; mkdir -p $O
+timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_steps20.log 2>$O/bench_steps20.err || { tail -5 $O/bench_steps20.err; exit 1; }
+tail -1 $O/bench_steps20.log > $O/r03_bench_steps20_line.json
 echo "[progress] steps20 bench done"
 bash tools/probes/run_artifacts.sh || exit 1
 echo "[progress] default bench + kernel stats + microbench done"
