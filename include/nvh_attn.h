@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NVH_VERSION 205          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16 */
+#define NVH_VERSION 206          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode */
 
 /* dtype codes */
 #define NVH_BF16 0
@@ -106,7 +106,8 @@ int nvh_paged_decode(void* out, const void* q, const void* k_cache, const void* 
  *                          the finer passes balance the workgroups better; measured -2.5 % on average there, +1..12 % with more chunks)
  *   NVH_DECODE_CHUNKED_P128 / _P256 / _P64  the chunked kernel with the pass size forced: hd 64 takes 128 or 256 (16- / 32-token wave tiles),
  *                          hd 128 takes 128 or 64 (four waves x 32- / 16-token tiles; the default picks 64 where a pair is split over at most
- *                          8 workgroups: -5 % at Qwen2-7B's per-rank shape 7/1/128, bs 32); a size the head_dim does not have is ignored
+ *                          8 workgroups: -5 % at Qwen2-7B's per-rank shape 7/1/128, bs 32); a size the head_dim does not have forces the full
+ *                          pass (256 at hd 64, 128 at hd 128).  _P128 at hd 64 and _P64 at hd 128 exist with 8 / 4 waves only and override `waves`
  *   NVH_DECODE_SPLIT_MFMA  the single-pass MFMA split kernel + a combine launch (flash-decoding in two launches).
  *   NVH_DECODE_SPLIT_VALU  north_star's literal form: VALU dot products with wavefront-level (DPP / permlane) max and sum
  *                          reductions, no MFMA; groups of at most 8 query heads per kv head; + the combine launch.
@@ -117,6 +118,20 @@ int nvh_paged_decode_variant(int variant, int waves, int chunks, void* out, cons
                              int batch, int h, int kvh, int hd, int block_size, int max_blocks,
                              int64_t q_row_stride, int64_t bt_row_stride, float scale,
                              int dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * What nvh_paged_decode_variant(variant, waves, chunks, ...) launches at these shapes (nvh_paged_decode: NVH_DECODE_CHUNKED, 0, 0): host-only, no
+ * device work.  cus = the device's compute units, 0 = the current device's.  All routing rules live in csrc/plan.h; this reports their result.
+ * Returns 0, or NVH_E_SHAPE for a request the shape does not allow.
+ */
+typedef struct nvh_decode_plan {
+    int32_t impl;                   /* NVH_DECODE_CHUNKED / _SPLIT_MFMA / _SPLIT_VALU */
+    int32_t waves;                  /* waves per workgroup actually launched */
+    int32_t pass_tokens;            /* tokens per pass actually launched (split kernels: per workgroup) */
+    int32_t chunks;                 /* chunked kernel: workgroups per (sequence, kv head) */
+    int32_t num_splits;             /* full passes the longest possible context has (sizes the workspace records) */
+} nvh_decode_plan;
+int nvh_plan_decode(nvh_decode_plan* plan, int variant, int waves, int chunks, int batch, int h, int kvh, int hd, int block_size, int max_blocks, int cus);
 
 /*
  * nvh_paged_decode that ALSO writes the bf16 result in MFMA-fragment order (out_packed: [ceil(batch/16)][h*hd/32][64][8],
@@ -176,7 +191,7 @@ int nvh_prefill_varlen(void* out, const void* q, const void* k, const void* v,
  *                NVH_PREFILL_TILED_F16V (a MEASUREMENT variant, not a drop-in: block_tables must be NULL): `v` holds the values as IEEE fp16 rows,
  *                converted by the caller (same layout and strides); P is rounded to fp16 and P V runs as one fp16 MFMA per operand pair instead
  *                of the bf16 hi + lo pair.  Error 4.5e-4 on the reference goldens (hi + lo: 6e-6), |v| <= 65504 required; DESIGN.md section 12.2
- *   short_waves  waves per workgroup of the short-sequence kernel: 0 = auto, 8 or 16
+ *   short_waves  waves per workgroup of the short-sequence kernel: 0 = auto, 8 or 16 (head_dim 128 has the 8-wave form only: 16 runs 8 there)
  */
 enum { NVH_PREFILL_AUTO = 0, NVH_PREFILL_TILED = 1, NVH_PREFILL_SHORT = 2, NVH_PREFILL_TILED_F16V = 3 };
 int nvh_prefill_varlen_variant(int kernel, int short_waves, void* out, const void* q, const void* k, const void* v,
@@ -214,6 +229,27 @@ int nvh_prefill_varlen_pv16(void* out, const void* q, const void* k, const void*
                             const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int batch, int max_seqlen_q, int max_seqlen_k, int total_k,
                             int h, int kvh, int hd, int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride,
                             float scale, int dtype, int out_dtype, void* scratch, size_t scratch_bytes, void* stream);
+
+/*
+ * What a prefill call launches at these shapes: host-only, no device work.  kernel / short_waves as nvh_prefill_varlen_variant (0, 0 = what
+ * nvh_prefill_varlen passes); pv: NVH_PV_NEVER = nvh_prefill_varlen, NVH_PV_ALWAYS = nvh_prefill_varlen_pv16, NVH_PV_AUTO = fp16 P V where it pays and is
+ * invisible (the rule is csrc/plan.h's): a caller that wants the default behaviour asks with AUTO, calls nvh_prefill_varlen_pv16 (with scratch_bytes of
+ * scratch) when pv_form is an fp16 form and nvh_prefill_varlen otherwise.  paged: block_tables != NULL.  cus as nvh_plan_decode.
+ * Returns 0, or NVH_E_SHAPE for a request the shape does not allow (nvh_last_error() says why).
+ */
+enum { NVH_PV_NEVER = 0, NVH_PV_ALWAYS = 1, NVH_PV_AUTO = 2 };
+enum { NVH_PV_EXACT = 0, NVH_PV_F16_SCRATCH = 1, NVH_PV_F16_IN_KERNEL = 2, NVH_PV_F16_HANDED_IN = 3 };   /* hi + lo bf16 P; fp16 copy of V in scratch; converted by the short kernel; NVH_PREFILL_TILED_F16V */
+enum { NVH_PLAN_SHORT = 0, NVH_PLAN_TILED = 1 };
+typedef struct nvh_prefill_plan {
+    int32_t kernel;                 /* NVH_PLAN_SHORT / NVH_PLAN_TILED */
+    int32_t paged;                  /* the tiled kernel reads K / V through the block table */
+    int32_t q_subtiles;             /* tiled kernel: 16-row query sub-tiles per wave, 1 or 2 */
+    int32_t short_waves;            /* short kernel: waves per workgroup actually launched, 8 or 16 (head_dim 128: always 8); 0 for the tiled kernel */
+    int32_t pv_form;                /* NVH_PV_EXACT / _F16_SCRATCH / _F16_IN_KERNEL / _F16_HANDED_IN */
+    size_t scratch_bytes;           /* _F16_SCRATCH: nvh_prefill_pv16_scratch_bytes(total_k, kvh, hd); 0 otherwise */
+} nvh_prefill_plan;
+int nvh_plan_prefill(nvh_prefill_plan* plan, int kernel, int short_waves, int pv, int out_dtype, int paged,
+                     int batch, int max_seqlen_q, int max_seqlen_k, int total_k, int kvh, int hd, int cus);
 
 /*
  * "Next" row: the step immediately before attention, fused into one launch.

@@ -29,6 +29,16 @@ int check_launch(const char* what) {
     return 0;
 }
 
+// the only place that asks the device for its CU count
+int device_cus() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return v;
+    }();
+    return n;
+}
+
 // diagnostic builds (-DNVH_STAMPS) set this through nvh_debug_set_stamps; always null in the shipped library
 static unsigned long long* g_stamps = nullptr;
 
@@ -84,30 +94,30 @@ int nvh_store_kvcache(const void* k, const void* v, void* k_cache, void* v_cache
                                 k_row_stride, v_row_stride, (hipStream_t)stream);
 }
 
-static constexpr size_t kDecodeTicketBytes = 65536;       // 512 tickets, one per 128-byte line (pairs are split over chunks only when there are few of them)
-static constexpr size_t kDecodeSyncBytes = 8192;          // behind the tickets: the ready / done counters and the status word of nvh_qkv_rope_attend
-static constexpr size_t kDecodeHeaderBytes = kDecodeTicketBytes + kDecodeSyncBytes;
-// nvh_prefill_varlen_pv16 scratch: one int32 range flag per kPv16GroupRows rows (padded to 256 bytes), then the fp16 rows
-static size_t pv16_header_bytes(int total_k) { return ((size_t)((total_k + nvh::kPv16GroupRows - 1) / nvh::kPv16GroupRows) * 4 + 255) / 256 * 256; }
-
-static int decode_num_splits(int hd, int max_blocks, int block_size) {
-    const int split = decode_split_tokens(hd);
-    const int64_t cap = (int64_t)max_blocks * block_size;
-    int n = (int)((cap + split - 1) / split);
-    return n < 1 ? 1 : n;
-}
-
 size_t nvh_paged_decode_workspace(int batch, int h, int hd, int max_blocks, int block_size) {
     if (batch <= 0 || h <= 0 || (hd != 64 && hd != 128) || max_blocks <= 0 || block_size <= 0) return 0;
     const size_t parts = (size_t)batch * h * decode_num_splits(hd, max_blocks, block_size);
-    // a fixed header of arrival tickets (one per (sequence, kv head); the SAME bytes whatever the shape, so that one
-    // workspace serves calls of different shapes), then the partial records
+    // the fixed header (kernels.h), then the partial records
     // (twice the packed size: chunk records are padded to 256-byte boundaries, at most a factor two at one query head per kv head)
-    return kDecodeHeaderBytes + 2 * parts * (size_t)(hd + 2) * sizeof(float);
+    return kWsHeaderBytes + 2 * parts * (size_t)(hd + 2) * sizeof(float);
 }
 
-// validates the call and fills `a`; returns 1 when there is nothing to do (batch == 0), 0 when `a` is ready, < 0 on rejection
-static int paged_decode_args(DecodeArgs& a, void* out, void* out_packed, const void* q, const void* k_cache, const void* v_cache,
+// plan query (host-only): cus == 0 = the current device's
+int nvh_plan_decode(nvh_decode_plan* plan, int variant, int waves, int chunks, int batch, int h, int kvh, int hd, int block_size, int max_blocks, int cus) {
+    if (!plan) { set_error("plan_decode: null pointer"); return NVH_E_NULL; }
+    if (variant < NVH_DECODE_CHUNKED || variant > NVH_DECODE_CHUNKED_P64 || (waves != 0 && waves != 4 && waves != 8) || chunks < 0 ||
+        batch <= 0 || h <= 0 || kvh <= 0 || (hd != 64 && hd != 128) || block_size <= 0 || max_blocks <= 0 || cus < 0) {
+        set_error("plan_decode: variant %d / waves %d / chunks %d or the shape not supported", variant, waves, chunks);
+        return NVH_E_SHAPE;
+    }
+    const DecodePlan p = plan_decode(variant, waves, chunks, DecodeShape{batch, h, kvh, hd, block_size, max_blocks, kMaxSplitPairs}, cus ? cus : device_cus());
+    if (p.error) { set_error("plan_decode: %s", p.message); return p.error; }
+    *plan = nvh_decode_plan{p.impl, p.waves, p.pass_tokens, p.chunks, p.num_splits};
+    return 0;
+}
+
+// validates the call, fills `a` and its plan `p`; returns 1 when there is nothing to do (batch == 0), 0 when `a` is ready, < 0 on rejection
+static int paged_decode_args(DecodeArgs& a, DecodePlan& p, void* out, void* out_packed, const void* q, const void* k_cache, const void* v_cache,
                              const int32_t* block_tables, const int32_t* context_lens,
                              int batch, int h, int kvh, int hd, int block_size, int max_blocks,
                              int64_t q_row_stride, int64_t bt_row_stride, float scale,
@@ -118,7 +128,8 @@ static int paged_decode_args(DecodeArgs& a, void* out, void* out_packed, const v
         set_error("paged_decode: variant %d / waves %d / chunks %d not supported", variant, waves, chunks);
         return NVH_E_SHAPE;
     }
-    if (variant == NVH_DECODE_SPLIT_VALU && h / (kvh > 0 ? kvh : 1) > 8) { set_error("paged_decode: the VALU variant serves groups of at most 8 query heads"); return NVH_E_SHAPE; }
+    p = plan_decode(variant, waves, chunks, DecodeShape{batch, h, kvh, hd, block_size, max_blocks, kMaxSplitPairs}, device_cus());
+    if (p.error) { set_error("paged_decode: %s", p.message); return p.error; }
     if (out_packed && (!aligned16(out_packed) || ((int64_t)h * hd) % 32)) { set_error("paged_decode: out_packed needs 16-byte alignment and h*hd %% 32 == 0"); return NVH_E_ALIGN; }
     if (dtype != NVH_BF16 || (out_dtype != NVH_BF16 && out_dtype != NVH_F32)) {
         set_error("paged_decode: dtype %d / out_dtype %d unsupported", dtype, out_dtype);
@@ -156,16 +167,11 @@ static int paged_decode_args(DecodeArgs& a, void* out, void* out_packed, const v
     a.context_lens = context_lens;
     a.batch = batch; a.h = h; a.kvh = kvh; a.hd = hd;
     a.block_size = block_size; a.max_blocks = max_blocks;
-    a.num_splits = decode_num_splits(hd, max_blocks, block_size);
-    // (tickets are only drawn when a (sequence, kv head) pair is split over several workgroups, i.e. when batch * kvh is small)
-    a.chunks = decode_chunks(batch, kvh, a.num_splits, chunks);
-    // (decode_chunks never splits more pairs than the header has tickets for: 512, one per 128-byte line)
+    a.num_splits = p.num_splits;
+    a.chunks = p.chunks;                                         // (never more split pairs than the header has tickets for: plan.h decode_chunks)
     a.counters = reinterpret_cast<unsigned*>(workspace);
-    a.ws_acc = reinterpret_cast<float*>((unsigned char*)workspace + kDecodeHeaderBytes);
+    a.ws_acc = reinterpret_cast<float*>((unsigned char*)workspace + kWsRecordBase);
     a.ws_ml = a.ws_acc + (size_t)batch * h * a.num_splits * hd;
-    // (a pass size the head_dim does not have — 256 at hd 128, 64 at hd 64 — leaves the default choice in place)
-    a.impl = variant >= NVH_DECODE_CHUNKED_P128 ? NVH_DECODE_CHUNKED : variant; a.waves = waves;
-    a.pass_tokens = variant == NVH_DECODE_CHUNKED_P128 ? 128 : (variant == NVH_DECODE_CHUNKED_P256 ? 256 : (variant == NVH_DECODE_CHUNKED_P64 ? 64 : 0));
     a.out_packed = (uint16_t*)out_packed;
     a.q_row_stride = q_row_stride; a.bt_row_stride = bt_row_stride;
     a.scale_log2 = scale * kLog2e;
@@ -181,10 +187,11 @@ static int paged_decode_impl(void* out, void* out_packed, const void* q, const v
                              int dtype, int out_dtype, void* workspace, size_t workspace_bytes, void* stream,
                              int variant = NVH_DECODE_CHUNKED, int waves = 0, int chunks = 0) {
     DecodeArgs a;
-    const int rc = paged_decode_args(a, out, out_packed, q, k_cache, v_cache, block_tables, context_lens, batch, h, kvh, hd, block_size, max_blocks,
+    DecodePlan p;
+    const int rc = paged_decode_args(a, p, out, out_packed, q, k_cache, v_cache, block_tables, context_lens, batch, h, kvh, hd, block_size, max_blocks,
                                      q_row_stride, bt_row_stride, scale, dtype, out_dtype, workspace, workspace_bytes, variant, waves, chunks);
     if (rc) return rc > 0 ? 0 : rc;
-    return launch_paged_decode(a, (hipStream_t)stream);
+    return launch_paged_decode(a, p, (hipStream_t)stream);
 }
 
 int nvh_paged_decode(void* out, const void* q, const void* k_cache, const void* v_cache,
@@ -230,18 +237,37 @@ int nvh_decode_step(void* out, const void* q, const void* k_new, const void* v_n
                             workspace, workspace_bytes, stream);
 }
 
+int nvh_plan_prefill(nvh_prefill_plan* plan, int kernel, int short_waves, int pv, int out_dtype, int paged,
+                     int batch, int max_seqlen_q, int max_seqlen_k, int total_k, int kvh, int hd, int cus) {
+    if (!plan) { set_error("plan_prefill: null pointer"); return NVH_E_NULL; }
+    if (kernel < NVH_PREFILL_AUTO || kernel > NVH_PREFILL_TILED_F16V || (short_waves != 0 && short_waves != 8 && short_waves != 16) ||
+        pv < NVH_PV_NEVER || pv > NVH_PV_AUTO || batch < 0 || max_seqlen_q < 0 || max_seqlen_k < 0 || kvh <= 0 || (hd != 64 && hd != 128) || cus < 0) {
+        set_error("plan_prefill: kernel %d / short_waves %d / pv %d or the shape not supported", kernel, short_waves, pv);
+        return NVH_E_SHAPE;
+    }
+    if (out_dtype != NVH_BF16 && out_dtype != NVH_F32) { set_error("plan_prefill: out_dtype %d unsupported", out_dtype); return NVH_E_DTYPE; }
+    const PrefillPlan p = plan_prefill(PrefillRequest{kernel, short_waves, pv, out_dtype == NVH_F32, paged != 0},
+                                       PrefillShape{batch, max_seqlen_q, max_seqlen_k, total_k, kvh, hd}, cus ? cus : device_cus());
+    if (p.error) { set_error("plan_prefill: %s", p.message); return p.error; }
+    *plan = nvh_prefill_plan{p.kernel, p.paged, p.q_subtiles, p.short_waves, p.pv, p.scratch_bytes};
+    return 0;
+}
+
 static int prefill_varlen_impl(int kernel, int short_waves, void* out, const void* q, const void* k, const void* v,
                        const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
                        const int32_t* block_tables, int batch, int max_seqlen_q, int max_seqlen_k,
                        int h, int kvh, int hd, int block_size, int max_blocks,
                        int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride,
                        int64_t bt_row_stride, float scale, int dtype, int out_dtype, void* stream,
-                       bool pv16 = false, int total_k = 0, void* pv16_scratch = nullptr, size_t pv16_scratch_bytes = 0) {
+                       bool pv16 = false, int total_k = 0, void* pv16_scratch = nullptr, size_t scratch_bytes = 0) {
     if (batch == 0 || max_seqlen_q == 0) return 0;
-    if (kernel < 0 || kernel > 3 || (kernel == 3 && block_tables) || (short_waves != 0 && short_waves != 8 && short_waves != 16)) {
+    if (kernel < 0 || kernel > 3 || (short_waves != 0 && short_waves != 8 && short_waves != 16)) {
         set_error("prefill_varlen: kernel %d / short_waves %d not supported", kernel, short_waves);
         return NVH_E_SHAPE;
     }
+    const PrefillPlan p = plan_prefill(PrefillRequest{kernel, short_waves, pv16 ? NVH_PV_ALWAYS : NVH_PV_NEVER, out_dtype == NVH_F32, block_tables != nullptr},
+                                       PrefillShape{batch, max_seqlen_q, max_seqlen_k, total_k, kvh, hd}, device_cus());
+    if (kernel == NVH_PREFILL_TILED_F16V && p.error) { set_error("prefill_varlen: %s", p.message); return p.error; }   // (its other refusals come behind the argument checks)
     if (dtype != NVH_BF16 || (out_dtype != NVH_BF16 && out_dtype != NVH_F32)) {
         set_error("prefill_varlen: dtype %d / out_dtype %d unsupported", dtype, out_dtype);
         return NVH_E_DTYPE;
@@ -278,43 +304,29 @@ static int prefill_varlen_impl(int kernel, int short_waves, void* out, const voi
     a.scale_log2 = scale * kLog2e;
     a.out_f32 = out_dtype == NVH_F32;
     a.stamps = g_stamps;
-    a.kernel = kernel; a.short_waves = short_waves;
-    if (pv16) {
-        if (block_tables) { set_error("prefill_varlen_pv16: not with a block table (V is read from the cache)"); return NVH_E_SHAPE; }
-        if (!nvh_prefill_pv16_uses_scratch(batch, max_seqlen_q, max_seqlen_k, kvh, hd)) {
-            // the short-sequence kernel's shapes: it converts its resident V images itself (head_dim 64, more than one key tile: below, the conversion
-            // costs what it saves; otherwise the kernel keeps hi + lo); scratch untouched
-            a.short_pv16 = hd == 64 && max_seqlen_k > 64;
-        } else {
-            // fp16 P V on an fp16 copy of V made here: [one range flag per 64 rows, padded to 256 bytes][total_k rows of kvh*hd fp16].  Two launches, no
-            // host read, nothing to clear: convert (every workgroup writes its group's flag), attend (a sequence with a flagged group falls back to `v`).
-            if (!pv16_scratch) { set_error("prefill_varlen_pv16: null scratch"); return NVH_E_NULL; }
-            if (total_k <= 0 || !aligned16(pv16_scratch) || pv16_scratch_bytes < nvh_prefill_pv16_scratch_bytes(total_k, kvh, hd)) {
-                set_error("prefill_varlen_pv16: scratch of %zu bytes, %zu needed for %d rows (16-byte aligned)", pv16_scratch_bytes,
-                          nvh_prefill_pv16_scratch_bytes(total_k, kvh, hd), total_k);
-                return NVH_E_WORKSPACE;
-            }
-            int32_t* flags = (int32_t*)pv16_scratch;
-            uint16_t* v16 = (uint16_t*)((char*)pv16_scratch + pv16_header_bytes(total_k));
-            rc = launch_bf16_rows_to_f16(v16, v, total_k, kvh * hd, v_row_stride, (int64_t)kvh * hd, flags, (hipStream_t)stream);
-            if (rc) return rc;
-            a.v16 = v16; a.v16_row_stride = (int64_t)kvh * hd; a.pv16_flags = flags; a.pv16_rows = total_k;
-            a.kernel = 1;                                        // the tiled kernel
+    if (p.error) { set_error("prefill_varlen: %s", p.message); return p.error; }
+    if (p.pv == NVH_PV_F16_SCRATCH) {
+        // fp16 P V on an fp16 copy of V made here: [one range flag per 64 rows, padded to 256 bytes][total_k rows of kvh*hd fp16].  Two launches, no
+        // host read, nothing to clear: convert (every workgroup writes its group's flag), attend (a sequence with a flagged group falls back to `v`).
+        if (!pv16_scratch) { set_error("prefill_varlen_pv16: null scratch"); return NVH_E_NULL; }
+        if (total_k <= 0 || !aligned16(pv16_scratch) || scratch_bytes < p.scratch_bytes) {
+            set_error("prefill_varlen_pv16: scratch of %zu bytes, %zu needed for %d rows (16-byte aligned)", scratch_bytes, p.scratch_bytes, total_k);
+            return NVH_E_WORKSPACE;
         }
+        int32_t* flags = (int32_t*)pv16_scratch;
+        uint16_t* v16 = (uint16_t*)((char*)pv16_scratch + pv16_header_bytes(total_k));
+        rc = launch_bf16_rows_to_f16(v16, v, total_k, kvh * hd, v_row_stride, (int64_t)kvh * hd, flags, (hipStream_t)stream);
+        if (rc) return rc;
+        a.v16 = v16; a.v16_row_stride = (int64_t)kvh * hd; a.pv16_flags = flags; a.pv16_rows = total_k;
     }
-    return launch_prefill_varlen(a, (hipStream_t)stream);
+    return launch_prefill_varlen(a, p, (hipStream_t)stream);
 }
 
 int nvh_prefill_pv16_uses_scratch(int batch, int max_seqlen_q, int max_seqlen_k, int kvh, int hd) {
-    (void)hd;
-    const bool short_kernel = max_seqlen_k <= 128 && max_seqlen_q <= max_seqlen_k && (int64_t)batch * kvh >= 128;     // launch_short's rule (prefill_mfma.hip)
-    return short_kernel ? 0 : 1;
+    return plan_prefill(PrefillRequest{NVH_PREFILL_AUTO, 0, NVH_PV_ALWAYS, 0, 0}, PrefillShape{batch, max_seqlen_q, max_seqlen_k, 0, kvh, hd}, 0).pv == NVH_PV_F16_SCRATCH;
 }
 
-size_t nvh_prefill_pv16_scratch_bytes(int total_k, int kvh, int hd) {
-    if (total_k <= 0 || kvh <= 0 || hd <= 0) return 0;
-    return pv16_header_bytes(total_k) + (size_t)total_k * kvh * hd * 2;
-}
+size_t nvh_prefill_pv16_scratch_bytes(int total_k, int kvh, int hd) { return pv16_scratch_bytes(total_k, kvh, hd); }
 
 int nvh_prefill_varlen_pv16(void* out, const void* q, const void* k, const void* v,
                             const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int batch, int max_seqlen_q, int max_seqlen_k, int total_k,
@@ -555,24 +567,25 @@ static int qkv_rope_attend_impl(int mode, uint32_t spin_limit, int missing_produ
     int rc = linear_args(l, qkv, dtype);
     if (rc) return rc > 0 ? 0 : rc;
     DecodeArgs d;
-    rc = paged_decode_args(d, attn_out, attn_out_packed, qkv->out, qkv->k_cache, qkv->v_cache, block_tables, context_lens, qkv->m, qkv->h, qkv->kvh,
+    DecodePlan p;
+    rc = paged_decode_args(d, p, attn_out, attn_out_packed, qkv->out, qkv->k_cache, qkv->v_cache, block_tables, context_lens, qkv->m, qkv->h, qkv->kvh,
                            qkv->hd, block_size, max_blocks, qkv->out_row_stride, bt_row_stride, scale, dtype, NVH_BF16, workspace, workspace_bytes);
     if (rc) return rc > 0 ? 0 : rc;
-    const bool can = qkv_attend_supported(l, d);
+    const DecodePlan one = qkv_attend_plan(p);
+    const bool can = qkv_attend_supported(l, d, one, device_cus());
     if (mode == 2 && !can) { set_error("qkv_rope_attend: this shape cannot run as one launch (hd 64, k <= 1024, packed x, folded norm, grid <= 2 x CUs)"); return NVH_E_SHAPE; }
     // mode 0 (what nvh_qkv_rope_attend runs) takes the measured winner: TWO launches.  On MI355X the one-launch form loses at every
     // decode shape tried (its K/V stream fills the memory system's queues in front of the very loads the hand-off
     // chain waits for); it stays reachable (mode 2) and under the same parity tests.
     if (mode == 2 && can) {
         if (fused_out) *fused_out = 1;
-        return launch_qkv_attend(l, d, (unsigned char*)workspace + kDecodeTicketBytes, spin_limit, missing_producers, l.pf_ptr, l.pf_bytes, (hipStream_t)stream);
+        return launch_qkv_attend(l, d, one, workspace, spin_limit, missing_producers, l.pf_ptr, l.pf_bytes, (hipStream_t)stream);
     }
     if (mode == 3 && d.hd == 64) {
-        // two launches, the first one's idle CUs touching the attention launch's first K/V images (its geometry: paged_decode.hip launch_chunked)
-        const int chunks = d.chunks;
+        // two launches, the first one's idle CUs touching the attention launch's first K/V images (its geometry: the plan's)
         l.pf_kv.k_cache = d.k_cache; l.pf_kv.v_cache = d.v_cache; l.pf_kv.block_tables = d.block_tables; l.pf_kv.context_lens = d.context_lens;
         l.pf_kv.bt_stride = d.bt_row_stride; l.pf_kv.batch = d.batch; l.pf_kv.kvh = d.kvh; l.pf_kv.hd = d.hd; l.pf_kv.block_size = d.block_size;
-        l.pf_kv.chunks = chunks; l.pf_kv.pass_tokens = (chunks >= 3 && chunks <= 5) ? 128 : 256;
+        l.pf_kv.chunks = p.chunks; l.pf_kv.pass_tokens = p.pass_tokens;
         l.pf_kv.passes = spin_limit ? (int)spin_limit : 1;            // (A/B: the variant's spin_limit argument carries the number of passes here)
         if (d.block_size % l.pf_kv.pass_tokens) l.pf_kv.k_cache = nullptr;
     }
@@ -581,7 +594,7 @@ static int qkv_rope_attend_impl(int mode, uint32_t spin_limit, int missing_produ
         if (qkv->x_packed || qkv->out_packed) { set_error("qkv_rope_attend: packed activations need the streaming kernel"); return NVH_E_SHAPE; }
         rc = launch_linear_small_m(l, (hipStream_t)stream);
     }
-    return rc ? rc : launch_paged_decode(d, (hipStream_t)stream);
+    return rc ? rc : launch_paged_decode(d, p, (hipStream_t)stream);
 }
 
 int nvh_qkv_rope_attend(const nvh_linear_desc* qkv, void* attn_out, void* attn_out_packed, const int32_t* block_tables, const int32_t* context_lens,
@@ -599,7 +612,7 @@ int nvh_qkv_rope_attend_variant(int mode, uint32_t spin_limit, int missing_produ
 
 int nvh_qkv_rope_attend_status(const void* workspace, uint32_t* timed_out) {
     if (!workspace || !timed_out) { set_error("qkv_rope_attend_status: null pointer"); return NVH_E_NULL; }
-    const hipError_t e = hipMemcpy(timed_out, (const unsigned char*)workspace + kDecodeTicketBytes + 4096, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy(timed_out, (const unsigned char*)workspace + kWsStatusOffset, sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) { set_error("qkv_rope_attend_status: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }

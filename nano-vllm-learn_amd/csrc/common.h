@@ -4,6 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// ---- A/B knobs that several files read: their defaults, once
+#ifndef NVH_DMA_AUX
+#define NVH_DMA_AUX 2        // cache policy of the once-read LDS-DMA streams (weights, K/V): 2 = nt, 0 = default.
+                             // nt measured -4.7 % on the decode step, -0.6 us per attention call (same box A/B, round 1)
+#endif
+#ifndef NVH_TICKET_WORDS
+#define NVH_TICKET_WORDS 32  // uint32 words between two arrival tickets: one ticket per 128-byte line; A/B builds: 1 = dense tickets (the round-1 layout)
+#endif
+
 namespace nvh {
 
 constexpr int kWave = 64;                       // CDNA wavefront width; never 32
@@ -123,5 +132,6 @@ __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcp
 // ---- host-side error plumbing ------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+int device_cus();            // compute units of the current device (256 on MI355X), read once: a device property, not a tuning knob
 
 }  // namespace nvh

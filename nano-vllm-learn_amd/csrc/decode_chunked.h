@@ -9,11 +9,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#ifndef NVH_DMA_AUX
-#define NVH_DMA_AUX 2        // cache policy of the once-read LDS-DMA streams (weights, K/V): 2 = nt, 0 = default.
-                             // nt measured -4.7 % on the decode step, -0.6 us per attention call (same box A/B, round 1)
-#endif
-
 namespace nvh {
 
 namespace {
@@ -46,14 +41,9 @@ namespace {
 #endif
 
 constexpr int MW = 4;
-#ifndef NVH_TICKET_WORDS
-#define NVH_TICKET_WORDS 32                      // A/B builds: 1 = dense tickets (the round-1 layout)
-#endif
 #ifndef NVH_REC_ALIGN
 #define NVH_REC_ALIGN 64                         // floats; A/B builds: 1 = records packed back to back (the round-1 layout)
 #endif
-constexpr int kTicketStride = NVH_TICKET_WORDS; // uint32 words between the tickets of two (sequence, kv head) pairs (= 128 bytes)
-constexpr int kMaxSplitPairs = 65536 / (4 * kTicketStride);   // tickets in the workspace's 64 KiB header: 512
 
 template <int D>
 struct MGeo {

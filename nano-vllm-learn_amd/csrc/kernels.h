@@ -4,13 +4,15 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "common.h"
+#include "plan.h"
+
 namespace nvh {
 
 int launch_store_kvcache(const void* k, const void* v, void* k_cache, void* v_cache,
                          const int32_t* slot_mapping, int n_tokens, int kvh, int hd,
                          int64_t k_row_stride, int64_t v_row_stride, hipStream_t stream);
 
-constexpr int kPv16GroupRows = 64;   // rows per range flag of the bf16 -> fp16 conversion (one conversion workgroup per group)
 int launch_bf16_rows_to_f16(void* out, const void* in, int n_rows, int row_elems, int64_t in_row_stride, int64_t out_row_stride, int32_t* group_flags, hipStream_t stream);
 
 struct DecodeArgs {
@@ -31,15 +33,21 @@ struct DecodeArgs {
     unsigned* counters;          // [B*KVH], zero before the launch, left zero by it
     int chunks;                  // workgroups per (sequence, kv head); passes are dealt to them round-robin
     uint16_t* out_packed;        // nullable: bf16 output also in MFMA-fragment order [ceil(B/16)][H*D/32][64][8] (pack_index)
-    int impl;                    // 0 chunked MFMA (default), 1 split MFMA + combine, 2 split VALU + combine (nvh_paged_decode_variant)
-    int waves;                   // chunked kernel: 0 / 8 = eight waves per workgroup, 4 = four
-    int pass_tokens;             // chunked kernel: 0 = chosen from the chunk count; forced: 128 / 256 at D = 64, 64 / 128 at D = 128
 };
+int launch_paged_decode(const DecodeArgs& a, const DecodePlan& p, hipStream_t stream);   // a.num_splits / a.chunks are p's
 
-// tokens one workgroup of the split kernel covers (static function of head_dim)
-int decode_split_tokens(int hd);
-int launch_paged_decode(const DecodeArgs& a, hipStream_t stream);
-int decode_chunks(int batch, int kvh, int num_splits, int forced);
+// ---- the decode workspace (bytes): [arrival tickets][ready counters][done counters][status word ...][partial records]
+constexpr int kTicketStride = NVH_TICKET_WORDS;                  // uint32 words between the tickets / counters of two (sequence, kv head) pairs / kv heads
+constexpr int kFusedCounters = 16;                               // ready and done counters of nvh_qkv_rope_attend's one-launch form: one per kv head each
+constexpr size_t kWsTicketBytes = 65536;                         // 512 tickets, one per 128-byte line (pairs are split over chunks only when there are few of them)
+constexpr int kMaxSplitPairs = (int)(kWsTicketBytes / (4 * kTicketStride));
+constexpr size_t kWsReadyOffset = kWsTicketBytes;
+constexpr size_t kWsDoneOffset = kWsReadyOffset + kFusedCounters * kTicketStride * 4;
+constexpr size_t kWsStatusOffset = kWsDoneOffset + kFusedCounters * kTicketStride * 4;
+constexpr size_t kWsHeaderBytes = kWsTicketBytes + 8192;         // the SAME bytes whatever the shape, so that one workspace serves calls of different shapes
+constexpr size_t kWsRecordBase = kWsHeaderBytes;
+static_assert(kWsStatusOffset == kWsTicketBytes + 2 * kFusedCounters * 4 * kTicketStride && kWsStatusOffset + 4 <= kWsHeaderBytes, "status word behind the counters, inside the header");
+static_assert((size_t)kMaxSplitPairs * 4 * kTicketStride == kWsTicketBytes && kWsRecordBase % 256 == 0, "one ticket per pair in the header; records 256-byte aligned");
 
 struct RopeStoreArgs {
     uint16_t* qkv;               // [N, (H+2KVH)*D] fused projection output, rotated in place
@@ -161,10 +169,10 @@ int allreduce_blocks(int rows, int hidden);
 int launch_allreduce_oneshot(const AllReduceArgs& a, int blocks, hipStream_t stream);
 
 // qkv projection (RoPE / store epilogue) + decode attention in ONE launch (qkv_attend.hip)
-size_t qkv_attend_sync_bytes(void);
-bool qkv_attend_supported(const LinearArgs& l, const DecodeArgs& d);
-int launch_qkv_attend(const LinearArgs& l, const DecodeArgs& d, void* sync, unsigned spin_limit, int missing_producers, const void* pf_ptr,
-                      int64_t pf_bytes, hipStream_t stream);
+DecodePlan qkv_attend_plan(const DecodePlan& two_launch);          // the consumer role's fixed shape, with the two-launch form's chunks
+bool qkv_attend_supported(const LinearArgs& l, const DecodeArgs& d, const DecodePlan& p, int cus);
+int launch_qkv_attend(const LinearArgs& l, const DecodeArgs& d, const DecodePlan& p, void* workspace, unsigned spin_limit, int missing_producers,
+                      const void* pf_ptr, int64_t pf_bytes, hipStream_t stream);
 
 struct PrefillArgs {
     void* out;                   // [Tq, H, D]
@@ -179,14 +187,12 @@ struct PrefillArgs {
     float scale_log2;
     int out_f32;
     unsigned long long* stamps;  // diagnostic builds only (NVH_STAMPS); null otherwise
-    int kernel;                  // 0 auto, 1 tiled kernel only, 2 short-sequence kernel (error if the shape does not allow it)
-    int short_waves;             // short-sequence kernel: 0 auto, 8 or 16 waves per workgroup
-    int short_pv16 = 0;                   // nvh_prefill_varlen_pv16 on the short-sequence kernel's shapes: convert V to fp16 inside the kernel (D = 64)
+    int v16_in_lds = 0;                   // short-sequence kernel operand, set by the launcher from the plan (NVH_PV_F16_IN_KERNEL): convert V to fp16 inside the kernel (D = 64)
     const uint16_t* v16 = nullptr;        // nvh_prefill_varlen_pv16: fp16 copy of the V rows [Tk, KVH, D] (row stride v16_row_stride) ...
     int64_t v16_row_stride = 0;
     int pv16_rows = 0;                    // rows converted (total_k of the call): a sequence reaching past them takes the exact form
     const int32_t* pv16_flags = nullptr;  // ... and one word per kPv16GroupRows rows, non-zero where a value did not fit fp16 (that sequence uses `v`, hi + lo bf16 P)
 };
-int launch_prefill_varlen(const PrefillArgs& a, hipStream_t stream);
+int launch_prefill_varlen(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream);
 
 }  // namespace nvh

@@ -32,10 +32,6 @@
 // a workgroup barrier the ticket holder joins.  A release/acquire fence pair here cost 4-5 us per launch (whole-L2
 // write-back + invalidate under 280 workgroups; profiles/r01_gemm_phase_stamps.txt).
 #include <cstdlib>
-#ifndef NVH_DMA_AUX
-#define NVH_DMA_AUX 2        // cache policy of the once-read LDS-DMA streams (weights, K/V): 2 = nt, 0 = default.
-                             // nt measured -4.7 % on the decode step, -0.6 us per attention call (same box A/B, round 1)
-#endif
 #include "common.h"
 #include "kernels.h"
 
@@ -45,9 +41,6 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef NVH_TICKET_WORDS
-#define NVH_TICKET_WORDS 32                        // A/B builds: 1 = dense tickets (the round-1 layout)
-#endif
 constexpr int kTicketWords = NVH_TICKET_WORDS;    // uint32 words between two tiles' arrival tickets: one ticket per 128-byte line
 constexpr int SW = 4;                          // waves per workgroup
 constexpr unsigned kMultiWgs = 512;            // workgroups of a MULTI launch (the LM head): two per CU, a power of two
@@ -69,16 +62,6 @@ __device__ __forceinline__ void st_sc1(float* p, float v) {
 }
 __device__ __forceinline__ float ld_sc1(const float* p) {
     return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
-// compute units of the current device (256 on MI355X), read once
-static int device_cus_ls() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
 }
 
 // workgroup barrier behind this wave's LDS traffic only.  __syncthreads() also waits vmcnt(0): inside the multi-tile loop that is the NEXT
@@ -638,7 +621,7 @@ __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
 static dim3 grid_of(const LinearArgs& a) {
     int extra = 0;
     if ((a.pf_ptr && a.pf_bytes >= 128) || a.pf_kv.k_cache) {
-        const int spare = device_cus_ls() - a.tiles * a.ksplit;
+        const int spare = device_cus() - a.tiles * a.ksplit;
         if (spare >= 8) extra = spare / a.ksplit;
     }
     return dim3(a.tiles + extra, a.ksplit);

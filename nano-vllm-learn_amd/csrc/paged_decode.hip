@@ -30,26 +30,9 @@
 // entries past ceil(ctx/bs) are never used, cache offsets are 64-bit.
 #include <stdlib.h>
 
-#ifndef NVH_DMA_AUX
-#define NVH_DMA_AUX 2        // cache policy of the once-read LDS-DMA streams (weights, K/V): 2 = nt, 0 = default.
-                             // nt measured -4.7 % on the decode step, -0.6 us per attention call (same box A/B, round 1)
-#endif
 #include "common.h"
 #include "kernels.h"
 #include "decode_chunked.h"
-
-#ifndef NVH_D128_HALF_RULE
-#define NVH_D128_HALF_RULE(chunks) ((chunks) <= 8)   // the chunk counts at which head_dim 128 takes 64-token passes by default.  Measured (same box,
-                             // B = 32, 64- against 128-token passes, ctx 1034 / 1536 / 2048 / 3072): 7/1/128 (8 chunks) 8.02 / 8.81 / 9.95 / 12.76 against
-                             // 8.25 / 9.27 / 10.23 / 12.74 us; 28/4/128 (2 chunks) -3 % everywhere; 16/8/128 (1 chunk) -0.2 .. -1 %; 7/1/128 at B = 64 (4 chunks)
-                             // -1.3 %, B = 16 (16 chunks) +1.3 %, B = 8 (32 chunks) +9 %: with 128-token passes twelve passes over eight chunks leave half the
-                             // workgroups with twice the tokens of the others; with many chunks the finer passes only add per-pass work
-#endif
-#ifndef NVH_D128_WAVES
-#define NVH_D128_WAVES 4     // waves per workgroup of the chunked kernel at head_dim 128 when the caller does not choose (4 or 8).
-                             // With 4-byte records 8 waves won (7/1/128 ctx 1536: 11.1 vs 12.1 us); since the records move as 16-byte items
-                             // 4 waves (32-token tiles, the k = 32 MFMA) win everywhere: 7/1/128 9.2 vs 9.6, 28/4/128 19.8 vs 20.6, 16/8/128 33.3 vs 34.0
-#endif
 
 namespace nvh {
 
@@ -517,43 +500,13 @@ int launch_valu_d(const DecodeArgs& a, int g, hipStream_t stream) {
     return -2;
 }
 
-template <int D>
+// one instantiation of the chunked kernel: which one is the plan's choice (plan.h), not this file's
+template <int D, int NW, int PASS>
 int launch_chunked(const DecodeArgs& a, int g, hipStream_t stream) {
-    // D = 64: 8 waves (two per SIMD; 32-token tiles) by default: 6.97 vs 7.44 us at ctx 1034, 8.36 vs 8.47 at 1536; D = 128: NVH_D128_WAVES;
-    // a.waves = 4 / 8 (nvh_paged_decode_variant) selects either shape.
-    const int waves = a.waves == 4 ? 4 : (a.waves == 8 ? 8 : (D == 64 ? 8 : NVH_D128_WAVES));
     dim3 grid(a.kvh, a.batch, a.chunks);
     const int bs_shift = (a.block_size & (a.block_size - 1)) == 0 ? __builtin_ctz(a.block_size) : -1;
-    if constexpr (D == 64) {
-        // Pass size at D = 64.  A pair split over 3-5 workgroups leaves each with one or two 256-token passes: whenever the pass count is not a
-        // multiple of the chunk count some workgroups carry twice the tokens of the others and the call takes as long as they do.  128-token
-        // passes (16-token wave tiles, the k = 16 MFMA) balance them: B = 32 (4 chunks) -0.5 / -1.9 / -6.6 / -4.0 / +1.9 / -3.7 / -1.9 % at ctx
-        // 600 / 1034 / 1300 / 1536 / 1800 / 2500 / 3300, B = 40 (3 chunks) -2.9 % on average, B = 24 (5) -1.2 %.  With 8 and more chunks (small
-        // batches) the passes outnumber nothing and the doubled per-pass work costs +1..12 %; with 2 chunks (B = 64) it is a wash.
-        const bool half_passes = a.pass_tokens == 128 || (a.pass_tokens == 0 && waves == 8 && a.chunks >= 3 && a.chunks <= 5);
-        if (half_passes) {
-            hipLaunchKernelGGL((paged_decode_chunked_kernel<D, 8, 128>), grid, dim3(8 * 64), 0, stream, a.context_lens, a.block_tables, a.k_cache, a.v_cache,
-                               a.kvh, a.block_size, a.max_blocks, a.chunks, (int)a.bt_row_stride, bs_shift, a, g);
-            return check_launch("paged_decode_chunked");
-        }
-    }
-    if constexpr (D == 128) {
-        // Pass size at D = 128: 64-token passes (four waves x 16-token tiles, the k = 16 MFMA) where 128-token passes leave some workgroups of a pair
-        // with twice the tokens of the others (NVH_D128_HALF_RULE below; a.pass_tokens = 64 / 128 forces either)
-        const bool half_passes = a.pass_tokens == 64 || (a.pass_tokens == 0 && a.waves == 0 && NVH_D128_HALF_RULE(a.chunks));   // (pass_tokens 128 forces the full pass)
-        if (half_passes) {
-            hipLaunchKernelGGL((paged_decode_chunked_kernel<D, 4, 64>), grid, dim3(4 * 64), 0, stream, a.context_lens, a.block_tables, a.k_cache, a.v_cache,
-                               a.kvh, a.block_size, a.max_blocks, a.chunks, (int)a.bt_row_stride, bs_shift, a, g);
-            return check_launch("paged_decode_chunked");
-        }
-    }
-    if (waves == 8) {
-        hipLaunchKernelGGL((paged_decode_chunked_kernel<D, 8>), grid, dim3(8 * 64), 0, stream, a.context_lens, a.block_tables, a.k_cache, a.v_cache,
-                           a.kvh, a.block_size, a.max_blocks, a.chunks, (int)a.bt_row_stride, bs_shift, a, g);
-        return check_launch("paged_decode_chunked");
-    }
-    hipLaunchKernelGGL((paged_decode_chunked_kernel<D, 4>), grid, dim3(4 * 64), 0, stream, a.context_lens, a.block_tables, a.k_cache, a.v_cache, a.kvh,
-                       a.block_size, a.max_blocks, a.chunks, (int)a.bt_row_stride, bs_shift, a, g);
+    hipLaunchKernelGGL((paged_decode_chunked_kernel<D, NW, PASS>), grid, dim3(NW * 64), 0, stream, a.context_lens, a.block_tables, a.k_cache, a.v_cache,
+                       a.kvh, a.block_size, a.max_blocks, a.chunks, (int)a.bt_row_stride, bs_shift, a, g);
     return check_launch("paged_decode_chunked");
 }
 
@@ -567,44 +520,26 @@ int launch_mfma(const DecodeArgs& a, int g, hipStream_t stream) {
 
 }  // namespace
 
-int decode_split_tokens(int hd) { return hd == 64 ? MGeo<64>::SPLIT : MGeo<128>::SPLIT; }
 static_assert(MGeo<64>::SPLIT == Geo<64>::SPLIT && MGeo<128>::SPLIT == Geo<128>::SPLIT, "both split kernels share one workspace layout");
+static_assert(decode_split_tokens(64) == MGeo<64>::SPLIT && decode_split_tokens(128) == MGeo<128>::SPLIT, "the plan's pass size is the kernels'");
 
-int decode_max_group(void) { return 16; }
-
-// compute units of the current device (256 on MI355X), read once: a device property, not a tuning knob
-static int device_cus() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
-// workgroups per (sequence, kv head): one wave of workgroups over the chip, at most one per pass; `forced` > 0 (the
-// variant entry point, tests and A/B runs) overrides the choice
-int decode_chunks(int batch, int kvh, int num_splits, int forced) {
-    if ((int64_t)batch * kvh > kMaxSplitPairs) return 1;       // (more pairs than tickets: far more than CUs anyway)
-    const int cus = device_cus();
-    // floor, never nearest: every workgroup needs a CU to itself (134 KB of LDS), so a launch of more workgroups than CUs runs its
-    // surplus as a second round (measured, B = 48 / 28 / 36 at ctx 1536: 3 / 5 / 4 chunks 13.8 / 11.0 / 10.8 us against
-    // 10.1 / 8.0 / 8.5 with 2 / 4 / 3)
-    int c = forced > 0 ? forced : cus / (batch * kvh);
-    if (c < 1) c = 1;
-    return c > num_splits ? num_splits : c;
-}
-
-int launch_paged_decode(const DecodeArgs& a, hipStream_t stream) {
-    if (a.batch == 0) return 0;
+// maps the plan to a template instantiation and launches it; the forms that exist: (waves, pass) = (8, 256) (4, 256) (8, 128) at D = 64,
+// (4, 128) (8, 128) (4, 64) at D = 128; the split kernels (the older formulations, kept for A/B and parity-tested) + the combine launch
+int launch_paged_decode(const DecodeArgs& a, const DecodePlan& p, hipStream_t stream) {
     const int g = a.h / a.kvh;
-    // a.impl (nvh_paged_decode_variant): 0 = the chunked MFMA kernel (one launch; what nvh_paged_decode runs), 1 = single-pass MFMA
-    // split kernel + combine, 2 = VALU split kernel (groups <= 8) + combine — the older formulations, kept for A/B and parity-tested
-    const int impl = a.impl;
-    if (impl != 0 && a.out_packed) { set_error("paged_decode: out_packed needs the chunked kernel"); return -2; }
-    if (impl == 2) return a.hd == 64 ? launch_valu_d<64>(a, g, stream) : launch_valu_d<128>(a, g, stream);
-    if (impl == 1) return a.hd == 64 ? launch_mfma<64>(a, g, stream) : launch_mfma<128>(a, g, stream);
-    return a.hd == 64 ? launch_chunked<64>(a, g, stream) : launch_chunked<128>(a, g, stream);
+    if (p.impl != NVH_DECODE_CHUNKED && a.out_packed) { set_error("paged_decode: out_packed needs the chunked kernel"); return -2; }
+    if (p.impl == NVH_DECODE_SPLIT_VALU) return a.hd == 64 ? launch_valu_d<64>(a, g, stream) : launch_valu_d<128>(a, g, stream);
+    if (p.impl == NVH_DECODE_SPLIT_MFMA) return a.hd == 64 ? launch_mfma<64>(a, g, stream) : launch_mfma<128>(a, g, stream);
+    switch (a.hd * 10000 + p.waves * 1000 + p.pass_tokens) {
+        case 64 * 10000 + 8 * 1000 + 256: return launch_chunked<64, 8, 256>(a, g, stream);
+        case 64 * 10000 + 4 * 1000 + 256: return launch_chunked<64, 4, 256>(a, g, stream);
+        case 64 * 10000 + 8 * 1000 + 128: return launch_chunked<64, 8, 128>(a, g, stream);
+        case 128 * 10000 + 4 * 1000 + 128: return launch_chunked<128, 4, 128>(a, g, stream);
+        case 128 * 10000 + 8 * 1000 + 128: return launch_chunked<128, 8, 128>(a, g, stream);
+        case 128 * 10000 + 4 * 1000 + 64: return launch_chunked<128, 4, 64>(a, g, stream);
+    }
+    set_error("paged_decode: no chunked kernel with head_dim %d, %d waves, %d-token passes", a.hd, p.waves, p.pass_tokens);
+    return -2;
 }
 
 }  // namespace nvh

@@ -630,7 +630,7 @@ void prefill_short_kernel(const PrefillArgs a) {
     [[maybe_unused]] int sk_round = 0;
     bool use16 = false;                              // workgroup-uniform
     if constexpr (PV16) {
-        if (a.short_pv16) {
+        if (a.v16_in_lds) {
             uint32_t big = 0;                        // largest finite |v| of this lane's chunks, as fp32 bits
             for (int c = tid; c < n_tiles * (IMG / 16); c += NW * 64) {
                 const int tile = c / (IMG / 16), off = (c - tile * (IMG / 16)) * 16;
@@ -850,41 +850,27 @@ void prefill_short_kernel(const PrefillArgs a) {
 }
 
 template <int D, int QT>
-int launch_q(const PrefillArgs& a, hipStream_t stream) {
+int launch_tiled(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream) {
     dim3 grid(a.h, a.batch, (a.max_seqlen_q + 64 * QT - 1) / (64 * QT));
-    if (a.kernel == 3) {                                         // NVH_PREFILL_TILED_F16V: v holds fp16 rows (measurement variant; never paged)
+    if (p.pv == NVH_PV_F16_HANDED_IN) {                          // NVH_PREFILL_TILED_F16V: v holds fp16 rows (measurement variant; never paged)
         hipLaunchKernelGGL((prefill_varlen_kernel<D, false, QT, 1>), grid, dim3(256), 0, stream, a);
         return check_launch("prefill_varlen_f16v");
     }
-    if (a.v16) {                                                 // nvh_prefill_varlen_pv16: fp16 P V unless the conversion raised the guard
+    if (p.pv == NVH_PV_F16_SCRATCH) {                            // nvh_prefill_varlen_pv16: fp16 P V unless the conversion raised the guard
         hipLaunchKernelGGL((prefill_varlen_kernel<D, false, QT, 2>), grid, dim3(256), 0, stream, a);
         return check_launch("prefill_varlen_pv16");
     }
-    if (a.block_tables) hipLaunchKernelGGL((prefill_varlen_kernel<D, true, QT>), grid, dim3(256), 0, stream, a);
+    if (p.paged) hipLaunchKernelGGL((prefill_varlen_kernel<D, true, QT>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((prefill_varlen_kernel<D, false, QT>), grid, dim3(256), 0, stream, a);
     return check_launch("prefill_varlen");
 }
 
-// a.kernel (nvh_prefill_varlen_variant): 1 = never, 2 = whenever the shape allows (tests), 0 = when it also fills the chip
 template <int D>
-int launch_short(const PrefillArgs& a, hipStream_t stream, bool& taken) {
-    taken = false;
-    const int mode = (a.kernel == 1 || a.kernel == 3) ? 0 : a.kernel == 2 ? 2 : 1;
-    const int max_keys = 128;                                    // (256 keys with four resident tiles measured slower than the tiled kernel)
-    if (mode == 0 || a.block_tables || a.max_seqlen_k > max_keys || a.max_seqlen_q > a.max_seqlen_k) return 0;
-    if (mode != 2 && a.batch * a.kvh < 128) return 0;            // few sequences: the tiled kernel spreads heads and q-tiles over the CUs
-    taken = true;
+int launch_short(PrefillArgs a, const PrefillPlan& p, hipStream_t stream) {
+    a.v16_in_lds = p.pv == NVH_PV_F16_IN_KERNEL;
     dim3 grid(a.kvh, a.batch, NVH_SHORT_SPLIT);
-    // a wave's tile is a long dependent chain (QK -> max -> exp2 -> hi/lo -> PV): four waves per SIMD to fill it where the registers allow
-    // (measured, Qwen2-0.5B heads, S = 128: 256 workgroups 22.7 us with 16 waves against 25.2 with 8; 512 workgroups, two per CU,
-    // 37.4 us with 8 against 41.9 with 16; the tiled kernel 28.3 / 56)
-#ifdef NVH_SHORT_FORCE_WAVES                  // A/B builds
-    const int waves = a.short_waves ? a.short_waves : NVH_SHORT_FORCE_WAVES;
-#else
-    const int waves = a.short_waves ? a.short_waves : (a.batch * a.kvh >= 384 ? 8 : 16);
-#endif
-    if constexpr (D == 64) {
-        if (waves == 16) {
+    if constexpr (D == 64) {                                     // (the 16-wave instantiation exists at D = 64 only; the plan never asks for it elsewhere)
+        if (p.short_waves == 16) {
             hipLaunchKernelGGL((prefill_short_kernel<D, 2, 16>), grid, dim3(1024), 0, stream, a);
             return check_launch("prefill_short");
         }
@@ -894,27 +880,16 @@ int launch_short(const PrefillArgs& a, hipStream_t stream, bool& taken) {
 }
 
 template <int D>
-int launch_d(const PrefillArgs& a, hipStream_t stream) {
-    bool taken;
-    const int rc = launch_short<D>(a, stream, taken);
-    if (taken) return rc;
-    if (a.kernel == 2) { set_error("prefill_varlen: the short-sequence kernel needs max_seqlen_q <= max_seqlen_k <= 128 and no block table"); return -2; }
-#ifndef NVH_PREFILL_QT2_FROM
-#define NVH_PREFILL_QT2_FROM 2048            // D = 64: two 16-row sub-tiles per wave from this many query rows on (A/B builds change it)
-#endif
-#ifndef NVH_PREFILL_QT2_FROM_PV16
-#define NVH_PREFILL_QT2_FROM_PV16 512        // ... in the fp16 P V form: its two-sub-tile body fits 128 registers = 4 waves per SIMD (same-box A/B against 2048:
-                                             // S = 512 42.5 -> 40.5 us, S = 1024 62.8 -> 58.8, S = 1536 77.8 -> 74.0; profiles/r03_prefill_qt2_pv16_ab.txt)
-#endif
-    const bool two = D == 128 ? a.max_seqlen_q > 128 : a.max_seqlen_q >= (a.v16 ? NVH_PREFILL_QT2_FROM_PV16 : NVH_PREFILL_QT2_FROM);
-    return two ? launch_q<D, 2>(a, stream) : launch_q<D, 1>(a, stream);
+int launch_d(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream) {
+    if (p.kernel == NVH_PLAN_SHORT) return launch_short<D>(a, p, stream);
+    return p.q_subtiles == 2 ? launch_tiled<D, 2>(a, p, stream) : launch_tiled<D, 1>(a, p, stream);
 }
 
 }  // namespace
 
-int launch_prefill_varlen(const PrefillArgs& a, hipStream_t stream) {
-    if (a.batch == 0 || a.max_seqlen_q == 0) return 0;
-    return a.hd == 64 ? launch_d<64>(a, stream) : launch_d<128>(a, stream);
+// maps the plan (plan.h) to a template instantiation and launches it
+int launch_prefill_varlen(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream) {
+    return a.hd == 64 ? launch_d<64>(a, p, stream) : launch_d<128>(a, p, stream);
 }
 
 }  // namespace nvh

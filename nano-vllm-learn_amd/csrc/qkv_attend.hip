@@ -290,15 +290,6 @@ __global__ __launch_bounds__(QA_WAVES * 64) void qkv_attend_kernel(
                                                        (int)a.dec.bt_row_stride, a.bs_shift, a.dec, a.G, a.fs);
 }
 
-static int qa_device_cus() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 template <int MT>
 int launch_mt(const QkvAttendArgs& a, int tiles, int gz, hipStream_t stream) {
     const LinearArgs& l = a.lin;
@@ -309,41 +300,47 @@ int launch_mt(const QkvAttendArgs& a, int tiles, int gz, hipStream_t stream) {
 
 }  // namespace
 
-// bytes of the sync area (behind the ticket header of the decode workspace): 16 ready counters, 16 done counters (one per 128-byte
-// line each), then the status word
-size_t qkv_attend_sync_bytes(void) { return 8192; }
-
-// Can this (projection, attention) pair run as ONE launch?  Pure function of the static shapes (and the device's CU count).
-bool qkv_attend_supported(const LinearArgs& l, const DecodeArgs& d) {
-    if (l.epi != EPI_ROPE || l.norm_mode != 2 || !l.x_packed || l.hd != 64 || d.hd != 64) return false;
-    if (l.M <= 0 || l.M > 64 || l.M != d.batch || l.K % 64 != 0 || l.K / 64 > QA_WAVES * QA_PM) return false;
-    if (l.h != d.h || l.kvh != d.kvh || d.h % d.kvh != 0 || d.h / d.kvh > 16 || d.kvh > 15) return false;
-    if (d.out_f32 || l.out_stride % 8 != 0) return false;
-    const int tiles = (l.h + 2 * l.kvh) * (l.hd / 32);
-    const int chunks = decode_chunks(d.batch, d.kvh, d.num_splits, 0);
-    // every workgroup resident at once: two per CU by LDS (72 KB each) and threads (512 each)
-    return tiles + d.batch * d.kvh * chunks <= 2 * qa_device_cus() && d.batch * d.kvh <= 65536 / (4 * kTicketStride);
+// the consumer role's fixed shape as a plan: the chunked kernel, 8 waves, 128-token passes, the chunks of the two-launch form
+DecodePlan qkv_attend_plan(const DecodePlan& two_launch) {
+    DecodePlan p = two_launch;
+    p.impl = NVH_DECODE_CHUNKED; p.waves = QA_WAVES; p.pass_tokens = QA_PASS;
+    return p;
 }
 
-// l.out = the q rows [M, h*hd] (row stride l.out_stride) = d.q; sync = qkv_attend_sync_bytes() zero-filled bytes (left zero by every launch)
+static int producer_tiles(const LinearArgs& l) { return (l.h + 2 * l.kvh) * (l.hd / 32); }
+
+// Can this (projection, attention) pair run as ONE launch?  What the kernel is built for is checked here; whether its grid is resident at once is
+// the plan's rule (one_launch_fits, plan.h)
+bool qkv_attend_supported(const LinearArgs& l, const DecodeArgs& d, const DecodePlan& p, int cus) {
+    if (l.epi != EPI_ROPE || l.norm_mode != 2 || !l.x_packed || l.hd != 64 || d.hd != 64) return false;
+    if (l.M <= 0 || l.M > 64 || l.M != d.batch || l.K % 64 != 0 || l.K / 64 > QA_WAVES * QA_PM) return false;
+    if (l.h != d.h || l.kvh != d.kvh || d.h % d.kvh != 0 || d.h / d.kvh > 16 || d.kvh >= kFusedCounters) return false;
+    if (d.out_f32 || l.out_stride % 8 != 0) return false;
+    return one_launch_fits(producer_tiles(l), (int64_t)d.batch * d.kvh, p.chunks, kMaxSplitPairs, cus);
+}
+
+// l.out = the q rows [M, h*hd] (row stride l.out_stride) = d.q; workspace = the decode workspace (its counters zero-filled, left zero by every launch)
 // missing_producers > 0 (tests): the consumers wait for that many producers more than exist, i.e. every wait runs out
-int launch_qkv_attend(const LinearArgs& l, const DecodeArgs& d_in, void* sync, unsigned spin_limit, int missing_producers, const void* pf_ptr,
-                      int64_t pf_bytes, hipStream_t stream) {
+int launch_qkv_attend(const LinearArgs& l, const DecodeArgs& d_in, const DecodePlan& p, void* workspace, unsigned spin_limit, int missing_producers,
+                      const void* pf_ptr, int64_t pf_bytes, hipStream_t stream) {
+    if (p.impl != NVH_DECODE_CHUNKED || p.waves != QA_WAVES || p.pass_tokens != QA_PASS) {   // the one instantiation this file has
+        set_error("qkv_attend: the plan asks for %d waves / %d-token passes, the kernel has %d / %d", p.waves, p.pass_tokens, QA_WAVES, QA_PASS);
+        return -2;
+    }
     QkvAttendArgs a;
     a.lin = l;
     a.dec = d_in;
-    a.dec.chunks = decode_chunks(a.dec.batch, a.dec.kvh, a.dec.num_splits, 0);
-    a.dec.impl = 0; a.dec.waves = 8; a.dec.pass_tokens = QA_PASS;
+    a.dec.chunks = p.chunks;
     a.G = a.dec.h / a.dec.kvh;
     a.bs_shift = (a.dec.block_size & (a.dec.block_size - 1)) == 0 ? __builtin_ctz(a.dec.block_size) : -1;
     const int tph = l.hd / 32;
-    const int tiles = (l.h + 2 * l.kvh) * tph;
+    const int tiles = producer_tiles(l);
     const int per_z = a.dec.kvh * a.dec.batch;
     const int gz = (tiles + per_z - 1) / per_z;
-    unsigned* const s = reinterpret_cast<unsigned*>(sync);
-    a.fs.ready = s;
-    a.fs.done = s + 16 * kTicketStride;
-    a.fs.status = s + 32 * kTicketStride;
+    unsigned char* const ws = reinterpret_cast<unsigned char*>(workspace);
+    a.fs.ready = reinterpret_cast<unsigned*>(ws + kWsReadyOffset);
+    a.fs.done = reinterpret_cast<unsigned*>(ws + kWsDoneOffset);
+    a.fs.status = reinterpret_cast<unsigned*>(ws + kWsStatusOffset);
     a.fs.need = (unsigned)((a.G + 2) * tph + missing_producers);
     a.fs.consumers = (unsigned)(a.dec.batch * a.dec.chunks);
     a.fs.spin_limit = spin_limit ? spin_limit : (1u << 20);

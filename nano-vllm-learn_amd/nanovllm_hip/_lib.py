@@ -30,7 +30,20 @@ class LinearDesc(ctypes.Structure):
                 ("prefetch", ctypes.c_void_p), ("prefetch_bytes", ctypes.c_size_t)]
 
 
+class PrefillPlan(ctypes.Structure):
+    """nvh_prefill_plan (include/nvh_attn.h): what a prefill call launches, as csrc/plan.h decides it."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "paged", "q_subtiles", "short_waves", "pv_form")] + [("scratch_bytes", ctypes.c_size_t)]
+
+
+class DecodePlan(ctypes.Structure):
+    """nvh_decode_plan (include/nvh_attn.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("impl", "waves", "pass_tokens", "chunks", "num_splits")]
+
+
 EPI_NONE, EPI_SILU_MUL, EPI_RESIDUAL_ADD, EPI_ROPE_STORE = 0, 1, 2, 3
+PV_NEVER, PV_ALWAYS, PV_AUTO = 0, 1, 2                                                          # NVH_PV_* requests (nvh_plan_prefill)
+PV_EXACT, PV_F16_SCRATCH, PV_F16_IN_KERNEL, PV_F16_HANDED_IN = 0, 1, 2, 3                       # NVH_PV_* forms (nvh_prefill_plan.pv_form)
+PLAN_SHORT, PLAN_TILED = 0, 1                                                                   # NVH_PLAN_* (nvh_prefill_plan.kernel)
 PREFILL_KERNELS = {"auto": 0, "tiled": 1, "short": 2, "tiled_f16v": 3}                         # NVH_PREFILL_* (nvh_prefill_varlen_variant)
 DECODE_VARIANTS = {"chunked": 0, "split_mfma": 1, "split_valu": 2, "chunked_p128": 3, "chunked_p256": 4, "chunked_p64": 5}      # NVH_DECODE_* (nvh_paged_decode_variant)
 
@@ -57,6 +70,8 @@ _SIGS = {
                            [ctypes.c_int64] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "nvh_prefill_varlen_variant": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4 + [_c_i32p] * 3 + [ctypes.c_int] * 8 +
                                    [ctypes.c_int64] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_plan_prefill": (ctypes.c_int, [ctypes.POINTER(PrefillPlan)] + [ctypes.c_int] * 12),
+    "nvh_plan_decode": (ctypes.c_int, [ctypes.POINTER(DecodePlan)] + [ctypes.c_int] * 10),
     "nvh_prefill_pv16_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "nvh_prefill_pv16_uses_scratch": (ctypes.c_int, [ctypes.c_int] * 5),
     "nvh_prefill_varlen_pv16": (ctypes.c_int, [ctypes.c_void_p] * 4 + [_c_i32p] * 2 + [ctypes.c_int] * 7 + [ctypes.c_int64] * 3 +
