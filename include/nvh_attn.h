@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NVH_VERSION 206          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode */
+#define NVH_VERSION 207          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk */
 
 /* dtype codes */
 #define NVH_BF16 0
@@ -250,6 +250,33 @@ typedef struct nvh_prefill_plan {
 } nvh_prefill_plan;
 int nvh_plan_prefill(nvh_prefill_plan* plan, int kernel, int short_waves, int pv, int out_dtype, int paged,
                      int batch, int max_seqlen_q, int max_seqlen_k, int total_k, int kvh, int hd, int cus);
+
+/*
+ * nvh_prefill_varlen with the key range of every 64-row query tile shared out over `key_splits` workgroups: short query chunks over a long cached prefix
+ * (a prefix-cache hit, chunked prefill), where one workgroup per (head, sequence, q-tile) leaves most of the chip idle.  Same arguments, same semantics,
+ * same parity bar; bf16 hi + lo P V.  Each workgroup walks a contiguous share of the key tiles its q-tile can see, publishes its partial (un-normalised O,
+ * max, sum) to `workspace` and the q-tile's LAST ARRIVER merges the partials in split order and writes `out`: one launch, deterministic, no allocation,
+ * no host sync, legal under graph capture (the protocol is the decode kernel's).
+ *   key_splits   0 = the plan's choice (csrc/plan.h: 1 when the unsplit grid already has 2 workgroups per CU or more q-tiles than tickets, 512);
+ *                > 0 = forced (tests, A/B), clamped to the 64-key tiles of max_seqlen_k and to 16.  ONE split launches exactly what nvh_prefill_varlen
+ *                launches (bit-identical output; workspace may be NULL).
+ *   workspace    device memory of at least nvh_prefill_splitk_workspace(...) bytes with the SAME key_splits, 16-byte aligned, owned by the caller and
+ *                ZERO-FILLED once: [one arrival ticket per (sequence, head, q-tile), each on a 128-byte line of its own: 64 KiB][partial records
+ *                [q-tile][split][64 rows x (hd + 4) floats]].  Every launch returns the tickets it drew to zero, so one buffer serves all layers, shapes and
+ *                graph replays; ONE launch at a time per workspace; after a launch aborted mid-flight zero-fill it again.
+ * Returns NVH_E_NULL (workspace NULL with more than one split), NVH_E_WORKSPACE (too small), NVH_E_SHAPE (head_dim other than 64 / 128, key_splits < 0).
+ * nvh_prefill_splitk_workspace: 0 where the plan says one split.  nvh_plan_prefill_splitk: host-only, *key_splits = what a call with `forced` launches
+ * at these shapes; cus as nvh_plan_decode.
+ */
+size_t nvh_prefill_splitk_workspace(int batch, int max_seqlen_q, int max_seqlen_k, int h, int hd, int key_splits, int cus);
+int nvh_plan_prefill_splitk(int* key_splits, int forced, int batch, int max_seqlen_q, int max_seqlen_k, int h, int kvh, int hd, int paged, int cus);
+int nvh_prefill_varlen_splitk(void* out, const void* q, const void* k, const void* v,
+                              const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                              const int32_t* block_tables, int batch, int max_seqlen_q, int max_seqlen_k,
+                              int h, int kvh, int hd, int block_size, int max_blocks,
+                              int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride,
+                              int64_t bt_row_stride, float scale, int dtype, int out_dtype, void* stream,
+                              int key_splits, void* workspace, size_t workspace_bytes);
 
 /*
  * "Next" row: the step immediately before attention, fused into one launch.

@@ -259,14 +259,17 @@ static int prefill_varlen_impl(int kernel, int short_waves, void* out, const voi
                        int h, int kvh, int hd, int block_size, int max_blocks,
                        int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride,
                        int64_t bt_row_stride, float scale, int dtype, int out_dtype, void* stream,
-                       bool pv16 = false, int total_k = 0, void* pv16_scratch = nullptr, size_t scratch_bytes = 0) {
+                       bool pv16 = false, int total_k = 0, void* pv16_scratch = nullptr, size_t scratch_bytes = 0,
+                       int key_splits = -1, void* splitk_ws = nullptr, size_t splitk_ws_bytes = 0) {   // key_splits >= 0: nvh_prefill_varlen_splitk (0 = the plan's choice)
     if (batch == 0 || max_seqlen_q == 0) return 0;
     if (kernel < 0 || kernel > 3 || (short_waves != 0 && short_waves != 8 && short_waves != 16)) {
         set_error("prefill_varlen: kernel %d / short_waves %d not supported", kernel, short_waves);
         return NVH_E_SHAPE;
     }
-    const PrefillPlan p = plan_prefill(PrefillRequest{kernel, short_waves, pv16 ? NVH_PV_ALWAYS : NVH_PV_NEVER, out_dtype == NVH_F32, block_tables != nullptr},
-                                       PrefillShape{batch, max_seqlen_q, max_seqlen_k, total_k, kvh, hd}, device_cus());
+    const PrefillShape shape{batch, max_seqlen_q, max_seqlen_k, total_k, kvh, hd};
+    const PrefillPlan p = key_splits >= 0 ? plan_prefill_splitk(key_splits, block_tables != nullptr, out_dtype == NVH_F32, shape, h, kSplitkTicketUnits, device_cus())
+                                          : plan_prefill(PrefillRequest{kernel, short_waves, pv16 ? NVH_PV_ALWAYS : NVH_PV_NEVER, out_dtype == NVH_F32, block_tables != nullptr},
+                                                         shape, device_cus());
     if (kernel == NVH_PREFILL_TILED_F16V && p.error) { set_error("prefill_varlen: %s", p.message); return p.error; }   // (its other refusals come behind the argument checks)
     if (dtype != NVH_BF16 || (out_dtype != NVH_BF16 && out_dtype != NVH_F32)) {
         set_error("prefill_varlen: dtype %d / out_dtype %d unsupported", dtype, out_dtype);
@@ -319,7 +322,54 @@ static int prefill_varlen_impl(int kernel, int short_waves, void* out, const voi
         if (rc) return rc;
         a.v16 = v16; a.v16_row_stride = (int64_t)kvh * hd; a.pv16_flags = flags; a.pv16_rows = total_k;
     }
+    if (p.key_splits > 1) {
+        // [tickets, zero between launches][records]: nothing to clear here, every launch returns the tickets it drew to zero
+        const size_t need = splitk_workspace_bytes(prefill_splitk_units(batch, max_seqlen_q, h), p.key_splits, hd);
+        if (!splitk_ws) { set_error("prefill_varlen_splitk: null workspace with %d key splits", p.key_splits); return NVH_E_NULL; }
+        if (!aligned16(splitk_ws)) { set_error("prefill_varlen_splitk: workspace must be 16-byte aligned"); return NVH_E_ALIGN; }
+        if (splitk_ws_bytes < need) { set_error("prefill_varlen_splitk: workspace %zu B < required %zu B", splitk_ws_bytes, need); return NVH_E_WORKSPACE; }
+        a.key_splits = p.key_splits;
+        a.sk_tickets = reinterpret_cast<unsigned*>(splitk_ws);
+        a.sk_records = reinterpret_cast<float*>((unsigned char*)splitk_ws + kSplitkRecordBase);
+    }
     return launch_prefill_varlen(a, p, (hipStream_t)stream);
+}
+
+static bool splitk_shape_ok(const char* who, int forced, int batch, int max_seqlen_q, int max_seqlen_k, int h, int hd) {
+    if (forced < 0 || batch < 0 || max_seqlen_q < 0 || max_seqlen_k < 0 || h <= 0 || (hd != 64 && hd != 128)) {
+        set_error("%s: key_splits %d (>= 0), head_dim %d (64 or 128), or a negative size", who, forced, hd);
+        return false;
+    }
+    return true;
+}
+
+int nvh_plan_prefill_splitk(int* key_splits, int forced, int batch, int max_seqlen_q, int max_seqlen_k, int h, int kvh, int hd, int paged, int cus) {
+    (void)paged;                                                 // (packed rows and the paged cache split alike)
+    if (!key_splits) { set_error("plan_prefill_splitk: null pointer"); return NVH_E_NULL; }
+    if (!splitk_shape_ok("plan_prefill_splitk", forced, batch, max_seqlen_q, max_seqlen_k, h, hd)) return NVH_E_SHAPE;
+    if (kvh <= 0 || cus < 0) { set_error("plan_prefill_splitk: kvh %d / cus %d", kvh, cus); return NVH_E_SHAPE; }
+    *key_splits = prefill_key_splits(forced, batch, max_seqlen_q, max_seqlen_k, h, hd, kSplitkTicketUnits, cus ? cus : device_cus());
+    return 0;
+}
+
+size_t nvh_prefill_splitk_workspace(int batch, int max_seqlen_q, int max_seqlen_k, int h, int hd, int key_splits, int cus) {
+    if (!splitk_shape_ok("prefill_splitk_workspace", key_splits, batch, max_seqlen_q, max_seqlen_k, h, hd) || cus < 0) return 0;
+    const int s = prefill_key_splits(key_splits, batch, max_seqlen_q, max_seqlen_k, h, hd, kSplitkTicketUnits, cus ? cus : device_cus());
+    return splitk_workspace_bytes(prefill_splitk_units(batch, max_seqlen_q, h), s, hd);
+}
+
+int nvh_prefill_varlen_splitk(void* out, const void* q, const void* k, const void* v,
+                              const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                              const int32_t* block_tables, int batch, int max_seqlen_q, int max_seqlen_k,
+                              int h, int kvh, int hd, int block_size, int max_blocks,
+                              int64_t q_row_stride, int64_t k_row_stride, int64_t v_row_stride,
+                              int64_t bt_row_stride, float scale, int dtype, int out_dtype, void* stream,
+                              int key_splits, void* workspace, size_t workspace_bytes) {
+    if (batch == 0 || max_seqlen_q == 0) return 0;
+    if (!splitk_shape_ok("prefill_varlen_splitk", key_splits, batch, max_seqlen_q, max_seqlen_k, h, hd)) return NVH_E_SHAPE;
+    return prefill_varlen_impl(0, 0, out, q, k, v, cu_seqlens_q, cu_seqlens_k, block_tables, batch, max_seqlen_q, max_seqlen_k, h, kvh, hd,
+                               block_size, max_blocks, q_row_stride, k_row_stride, v_row_stride, bt_row_stride, scale, dtype, out_dtype, stream,
+                               false, 0, nullptr, 0, key_splits, workspace, workspace_bytes);
 }
 
 int nvh_prefill_pv16_uses_scratch(int batch, int max_seqlen_q, int max_seqlen_k, int kvh, int hd) {

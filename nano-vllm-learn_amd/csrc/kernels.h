@@ -49,6 +49,15 @@ constexpr size_t kWsRecordBase = kWsHeaderBytes;
 static_assert(kWsStatusOffset == kWsTicketBytes + 2 * kFusedCounters * 4 * kTicketStride && kWsStatusOffset + 4 <= kWsHeaderBytes, "status word behind the counters, inside the header");
 static_assert((size_t)kMaxSplitPairs * 4 * kTicketStride == kWsTicketBytes && kWsRecordBase % 256 == 0, "one ticket per pair in the header; records 256-byte aligned");
 
+// ---- the split-key prefill workspace (bytes): [arrival tickets][partial records [unit][split][64 rows x (hd + 4) floats]]; unit = (sequence, head, q-tile)
+constexpr size_t kSplitkTicketBytes = kWsTicketBytes;            // one ticket per unit, each on a 128-byte line of its own: a split launch has fewer units than 2 x CUs
+constexpr int kSplitkTicketUnits = (int)(kSplitkTicketBytes / (4 * kTicketStride));
+constexpr size_t kSplitkRecordBase = kSplitkTicketBytes;
+static_assert(kSplitkRecordBase % 256 == 0, "records 256-byte aligned");
+inline size_t splitk_workspace_bytes(int units, int key_splits, int hd) {
+    return key_splits > 1 ? kSplitkRecordBase + (size_t)units * key_splits * splitk_record_bytes(hd) : 0;
+}
+
 struct RopeStoreArgs {
     uint16_t* qkv;               // [N, (H+2KVH)*D] fused projection output, rotated in place
     const int64_t* positions;    // [N]
@@ -192,6 +201,10 @@ struct PrefillArgs {
     int64_t v16_row_stride = 0;
     int pv16_rows = 0;                    // rows converted (total_k of the call): a sequence reaching past them takes the exact form
     const int32_t* pv16_flags = nullptr;  // ... and one word per kPv16GroupRows rows, non-zero where a value did not fit fp16 (that sequence uses `v`, hi + lo bf16 P)
+    // split-key form (nvh_prefill_varlen_splitk with more than one split): workgroups per q-tile, the workspace's tickets and records
+    int key_splits = 1;
+    unsigned* sk_tickets = nullptr;       // [units] at kTicketStride words, zero before the launch, left zero by it
+    float* sk_records = nullptr;          // [units][key_splits][splitk_record_bytes(hd) / 4]
 };
 int launch_prefill_varlen(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream);
 

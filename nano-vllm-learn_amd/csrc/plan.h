@@ -49,6 +49,7 @@ struct PrefillPlan {
     int short_waves = 0;         // short kernel: waves per workgroup actually launched (8 or 16); 0 for the tiled kernel
     int pv = NVH_PV_EXACT;       // NVH_PV_EXACT / F16_SCRATCH / F16_IN_KERNEL / F16_HANDED_IN
     size_t scratch_bytes = 0;    // F16_SCRATCH: what the call needs
+    int key_splits = 1;          // > 1: the split-key form of the tiled kernel (plan_prefill_splitk), workgroups per q-tile
 };
 
 // nvh_prefill_varlen_pv16 scratch: one int32 range flag per kPv16GroupRows rows (padded to 256 bytes), then the fp16 rows
@@ -108,6 +109,61 @@ inline PrefillPlan plan_prefill(const PrefillRequest& r, const PrefillShape& s, 
     else p.q_subtiles = s.max_seqlen_q >= (p.pv == NVH_PV_F16_SCRATCH ? NVH_PREFILL_QT2_FROM_PV16 : NVH_PREFILL_QT2_FROM) ? 2 : 1;
     return p;
 }
+
+// ---- split-key prefill (nvh_prefill_varlen_splitk): workgroups per (sequence, head, 64-row q-tile), each walking a contiguous share of the key tiles
+// the q-tile can see.  The tiled kernel gives a q-tile ONE workgroup: few query rows against a long cached prefix leave most CUs idle.
+constexpr int kSplitkTileKeys = 64;          // keys per tile and query rows per q-tile of the split form (prefill_mfma.hip asserts it)
+constexpr int kSplitkMaxSplits = 16;         // absolute cap: records the last arriver of a q-tile merges
+constexpr int kSplitkTargetPerCu = 2;        // workgroups per CU the split grid is brought towards (floor, never beyond).  Measured, graph-replayed calls, us, same box,
+                                             // key_splits 1 / 2 / 3 / 4 / 6 / 8 / 12 / 16 (profiles/prefill_splitk_ab.txt):
+                                             //   14/2/64 8 x 128 vs 2048 (224 q-tiles): 33.4 / 28.5 / 28.9 / 31.2 / 38.0 / 46.3 / 62.2 / 93.7 -> 2 (448 workgroups)
+                                             //   14/2/64 4 x 512 vs 4096 (448 q-tiles): 72.9 / 72.6 / 75.3 / 76.4 / 89.0 / 104 / 148 / 231   -> 1 (nothing to gain at 1.75 per CU)
+constexpr int kSplitkMinTiles = 8;           // key tiles a split keeps at least: below, the record round trip outweighs the shorter walk
+                                             //   14/2/64 1 x 64 vs 4096 (14 q-tiles, 64 tiles): 62.2 / 35.9 / 26.9 / 21.9 / 18.8 / 16.8 / 16.6 / 17.8 -> 8 (flat from 8 to 12)
+                                             //   14/2/64 1 x 16 vs 4096:                        61.5 / 35.3 / 26.4 / 21.6 / 18.4 / 16.5 / 16.3 / 17.6 -> 8
+
+inline int prefill_splitk_units(int batch, int max_seqlen_q, int h) {
+    if (batch <= 0 || max_seqlen_q <= 0 || h <= 0) return 0;
+    const int64_t u = (int64_t)batch * h * ((max_seqlen_q + kSplitkTileKeys - 1) / kSplitkTileKeys);
+    return u > INT32_MAX ? INT32_MAX : (int)u;
+}
+
+// key splits of a prefill call; `forced` > 0 (tests and A/B runs) overrides the rule, clamped to the key tiles of max_seqlen_k and the cap.
+// ticket_units: q-tiles the workspace header has tickets for (kSplitkTicketUnits)
+inline int prefill_key_splits(int forced, int batch, int max_seqlen_q, int max_seqlen_k, int h, int hd, int ticket_units, int cus) {
+    (void)hd;
+    const int units = prefill_splitk_units(batch, max_seqlen_q, h);
+    const int tiles = (max_seqlen_k + kSplitkTileKeys - 1) / kSplitkTileKeys;
+    if (units < 1 || tiles < 2 || units > ticket_units) return 1;
+    int s;
+    if (forced > 0) {
+        s = forced;
+    } else {
+        if (units >= 2 * (int64_t)cus) return 1;                 // the unsplit grid already gives every CU two workgroups
+        s = (int)((int64_t)kSplitkTargetPerCu * cus / units);
+        if (s > tiles / kSplitkMinTiles) s = tiles / kSplitkMinTiles;
+    }
+    if (s > tiles) s = tiles;
+    if (s > kSplitkMaxSplits) s = kSplitkMaxSplits;
+    return s < 1 ? 1 : s;
+}
+
+// nvh_prefill_varlen_splitk: one split = exactly the plan of nvh_prefill_varlen; more = the tiled kernel's split-key form (64-row q-tiles, exact P V)
+inline PrefillPlan plan_prefill_splitk(int forced, int paged, int out_f32, const PrefillShape& s, int h, int ticket_units, int cus) {
+    PrefillPlan p = plan_prefill(PrefillRequest{NVH_PREFILL_AUTO, 0, NVH_PV_NEVER, out_f32, paged}, s, cus);
+    const int splits = prefill_key_splits(forced, s.batch, s.max_seqlen_q, s.max_seqlen_k, h, s.hd, ticket_units, cus);
+    if (p.error || splits <= 1) return p;
+    p.kernel = NVH_PLAN_TILED;
+    p.q_subtiles = 1;
+    p.short_waves = 0;
+    p.pv = NVH_PV_EXACT;
+    p.key_splits = splits;
+    return p;
+}
+
+// record of one split of one q-tile: 64 rows of [hd floats of un-normalised O | max (log2 domain) | sum | 0 | 0]; a multiple of 256 bytes at both head_dims
+constexpr size_t splitk_record_bytes(int hd) { return (size_t)kSplitkTileKeys * (hd + 4) * 4; }
+static_assert(splitk_record_bytes(64) % 256 == 0 && splitk_record_bytes(128) % 256 == 0, "records start on 256-byte boundaries");
 
 // ============================================================================================ decode
 struct DecodeShape { int batch, h, kvh, hd, block_size, max_blocks, ticket_pairs; };   // ticket_pairs: pairs the workspace header has tickets for (kMaxSplitPairs)

@@ -34,6 +34,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "prefill_splitk.h"
 
 namespace nvh {
 
@@ -160,8 +161,11 @@ __device__ __forceinline__ void prefill_tile_of_block(const PrefillArgs& a, int&
 // GUARD (nvh_prefill_varlen_pv16): `a.v` is the fp16 copy of V; the range flags of this sequence's rows are fetched FIRST, the first K image's DMA is
 // issued behind them, and only then are they looked at — so the check costs no memory latency of its own.  Returns false (nothing but that K image
 // touched) when a flag is set: the caller runs the exact body instead.
-template <int D, bool PAGED, int QT, bool F16V, bool GUARD = false>
-__device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsigned char* const lds, const int qt, const int head, const int b) {
+// SPLITK (prefill_splitk_kernel): the workgroup is split `split` of a.key_splits of its q-tile and walks only its share of the key tiles
+// (prefill_splitk.h); everything up to the end of the tile loop is the same code on a tile range that no longer starts at 0.
+template <int D, bool PAGED, int QT, bool F16V, bool GUARD = false, bool SPLITK = false>
+__device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsigned char* const lds, const int qt, const int head, const int b, const int split = 0) {
+    static_assert(!SPLITK || (QT == 1 && !F16V && !GUARD && BN == kSplitkTileKeys), "the split-key form: one sub-tile per wave, exact P V");
     constexpr int BM = 64 * QT;                      // query rows per workgroup (4 waves x QT x 16)
     constexpr int ROWB = D * 2;                      // LDS row, bytes
     constexpr int LPT = D / 8;                       // 16-byte chunks per row
@@ -203,6 +207,12 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
     const int n_tiles = (kv_end + BN - 1) / BN;
     const int wave_first_key = q0 + wave * WR + shift;            // last key the wave's FIRST row may see
     const int wave_last_key = wave_first_key + WR - 1;            // last key ANY row of this wave may see
+    int t_beg = 0, t_end = n_tiles;                               // the key tiles this workgroup walks
+    [[maybe_unused]] int live = 1;
+    if constexpr (SPLITK) {
+        splitk_range(n_tiles, a.key_splits, split, live, t_beg, t_end);
+        if (split >= live) return true;                           // more splits than key tiles: nothing to do, and no ticket drawn (the others count to `live`)
+    }
 
     // ---- staging: wave w issues DMA instructions w*NIW .. w*NIW+NIW-1 of the K image and of the V image.  Source address =
     // a wave-uniform base per tile (scalar arithmetic) + a loop-invariant 32-bit lane offset (row of the tile x row stride +
@@ -274,7 +284,7 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
         if (bad) return false;
         stage(0, 0, false, true);
     } else {
-        stage(0, 0);
+        stage(t_beg, 0);
     }
     // ---- Q fragments (B operand of S^T): Q[row][32*step + 8*lg .. +8]; plain loads issued BEHIND the first tile's DMA, so that a workgroup
     // pays one memory latency at its start, not two in a row (the counted wait of the first tile body leaves only tile 1's DMA in flight:
@@ -307,7 +317,7 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
     }
     auto tile_body = [&](auto bufc, const int it) {
         constexpr int buf = decltype(bufc)::value;
-        if (it + 1 < n_tiles) {
+        if (it + 1 < t_end) {
             stage(it + 1, buf ^ 1);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NIW) : "memory");       // tile `it` landed, tile it+1 in flight
         } else {
@@ -479,9 +489,9 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
         __builtin_amdgcn_s_barrier();                                            // ... and everyone's: tile it+2 may overwrite it
         asm volatile("" ::: "memory");
     };
-    for (int it = 0; it < n_tiles; it += 2) {
+    for (int it = t_beg; it < t_end; it += 2) {
         tile_body(std::integral_constant<int, 0>{}, it);
-        if (it + 1 < n_tiles) tile_body(std::integral_constant<int, 1>{}, it + 1);
+        if (it + 1 < t_end) tile_body(std::integral_constant<int, 1>{}, it + 1);
     }
 
     PF_STAMP(31);
@@ -490,6 +500,14 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
     for (int qs = 0; qs < QT; ++qs) {
         float l = sum_xor16(l_run[qs]);
         l = sum_xor32(l);
+        if constexpr (SPLITK) {
+            // more than one live split: publish the partial; only the q-tile's last arriver goes on, with all live records merged into (o, l).
+            // One live split (a q-tile that sees fewer than two key tiles) writes its rows directly and touches no workspace.
+            if (live > 1) {
+                const int unit = (b * a.h + head) * (int)gridDim.z + qt;
+                if (!splitk_handoff<D>(a, lds, unit, split, live, wave * WR + lq, lg, o[qs], m_run[qs], l)) return true;
+            }
+        }
         if (!q_ok[qs]) continue;
         const float inv = l > 0.f ? 1.f / l : 0.f;
         const int64_t orow = ((int64_t)(q_beg + my_q[qs]) * a.h + head) * D;
@@ -538,6 +556,19 @@ void prefill_varlen_kernel(const PrefillArgs a) {
     } else {
         prefill_varlen_body<D, PAGED, QT, PV == 1>(a, lds, qt, head, b);
     }
+}
+
+// Split-key form (nvh_prefill_varlen_splitk, more than one split): grid (H, B * key_splits, q-tiles).  prefill_tile_of_block reads the y dimension as
+// "sequences": its XCD-aware order then keeps the heads x q-tiles of one (sequence, SPLIT, kv head) — the workgroups that stream the same key range —
+// on one XCD's L2, heaviest q-tiles first.  One 16-row sub-tile per wave: a short query chunk has few rows and needs the workgroups.
+template <int D, bool PAGED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
+void prefill_splitk_kernel(const PrefillArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 2 * BN * D * 2];     // [buffer][K | V]
+    int qt, head, bs;
+    prefill_tile_of_block(a, qt, head, bs);
+    const int b = bs / a.key_splits;
+    prefill_varlen_body<D, PAGED, 1, false, false, true>(a, lds, qt, head, b, bs - b * a.key_splits);
 }
 
 // ---- short sequences: every key of a sequence fits in LDS (sk <= 64 * NKT) ---------------------------------------------------
@@ -866,6 +897,14 @@ int launch_tiled(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream)
 }
 
 template <int D>
+int launch_splitk(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream) {
+    dim3 grid(a.h, a.batch * a.key_splits, (a.max_seqlen_q + 63) / 64);
+    if (p.paged) hipLaunchKernelGGL((prefill_splitk_kernel<D, true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((prefill_splitk_kernel<D, false>), grid, dim3(256), 0, stream, a);
+    return check_launch("prefill_splitk");
+}
+
+template <int D>
 int launch_short(PrefillArgs a, const PrefillPlan& p, hipStream_t stream) {
     a.v16_in_lds = p.pv == NVH_PV_F16_IN_KERNEL;
     dim3 grid(a.kvh, a.batch, NVH_SHORT_SPLIT);
@@ -881,6 +920,7 @@ int launch_short(PrefillArgs a, const PrefillPlan& p, hipStream_t stream) {
 
 template <int D>
 int launch_d(const PrefillArgs& a, const PrefillPlan& p, hipStream_t stream) {
+    if (p.key_splits > 1) return launch_splitk<D>(a, p, stream);
     if (p.kernel == NVH_PLAN_SHORT) return launch_short<D>(a, p, stream);
     return p.q_subtiles == 2 ? launch_tiled<D, 2>(a, p, stream) : launch_tiled<D, 1>(a, p, stream);
 }

@@ -70,6 +70,10 @@ _SIGS = {
                            [ctypes.c_int64] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "nvh_prefill_varlen_variant": (ctypes.c_int, [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4 + [_c_i32p] * 3 + [ctypes.c_int] * 8 +
                                    [ctypes.c_int64] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_prefill_splitk_workspace": (ctypes.c_size_t, [ctypes.c_int] * 7),
+    "nvh_plan_prefill_splitk": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)] + [ctypes.c_int] * 9),
+    "nvh_prefill_varlen_splitk": (ctypes.c_int, [ctypes.c_void_p] * 4 + [_c_i32p] * 3 + [ctypes.c_int] * 8 +
+                                  [ctypes.c_int64] * 4 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]),
     "nvh_plan_prefill": (ctypes.c_int, [ctypes.POINTER(PrefillPlan)] + [ctypes.c_int] * 12),
     "nvh_plan_decode": (ctypes.c_int, [ctypes.POINTER(DecodePlan)] + [ctypes.c_int] * 10),
     "nvh_prefill_pv16_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),

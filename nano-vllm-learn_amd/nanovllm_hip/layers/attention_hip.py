@@ -17,7 +17,7 @@ from ..utils.context import get_context
 class Attention(nn.Module):
 
     def __init__(self, num_heads, head_dim, scale, num_kv_heads, block_size: int = 256, fused_decode: bool = True,
-                 prefill_pv_fp16=None):
+                 prefill_pv_fp16=None, prefill_key_splits=None):
         super().__init__()
         self.num_heads = num_heads
         self.head_dim = head_dim
@@ -28,6 +28,9 @@ class Attention(nn.Module):
         # prefill P V on the fp16 matrix pipe (ops.flash_attn_varlen_func pv_fp16): None = the library's rule (bf16 output, packed rows, >= 512 keys per sequence or config 5's short batches;
         # range-guarded, falls back by itself), False = never (P as bf16 hi + lo, 6e-6 instead of <= 2^-12 * max|v|), True = at every length
         self.prefill_pv_fp16 = prefill_pv_fp16
+        # prefix-cached / chunked prefill (Context.block_tables set): key splits per query tile (ops.flash_attn_varlen_func key_splits): None = off,
+        # "auto" = the library's rule, an int = forced
+        self.prefill_key_splits = prefill_key_splits
         self.k_cache = self.v_cache = torch.tensor([])
 
     def rope_store_attend(self, qkv, positions, cos_sin, q_norm_weight=None, k_norm_weight=None, eps=1e-6):
@@ -85,7 +88,8 @@ class Attention(nn.Module):
                                            max_seqlen_q=context.max_seqlen_q, cu_seqlens_q=context.cu_seqlens_q,
                                            max_seqlen_k=context.max_seqlen_k, cu_seqlens_k=context.cu_seqlens_k,
                                            softmax_scale=self.scale, causal=True, block_table=context.block_tables,
-                                           pv_fp16=self.prefill_pv_fp16 if context.block_tables is None else False)
+                                           pv_fp16=self.prefill_pv_fp16 if context.block_tables is None else False,
+                                           key_splits=self.prefill_key_splits if context.block_tables is not None else None)
         else:
             if not have_cache:
                 raise RuntimeError("decode needs an allocated KV cache (k_cache/v_cache not bound)")

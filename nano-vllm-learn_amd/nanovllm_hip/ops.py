@@ -185,7 +185,7 @@ PV16_MIN_KEYS = 512       # fp16 P V (nvh_prefill_varlen_pv16) by default from t
 
 
 def flash_attn_varlen_func(q, k, v, max_seqlen_q, cu_seqlens_q, max_seqlen_k, cu_seqlens_k, softmax_scale=None,
-                           causal=True, block_table=None, out_dtype=None, kernel=None, short_waves=0, pv_fp16=None):
+                           causal=True, block_table=None, out_dtype=None, kernel=None, short_waves=0, pv_fp16=None, key_splits=None):
     """Packed varlen causal attention, drop-in for the call at attention.py:93-96.
 
     q [Tq, H, D]; without block_table k/v are [Tk, KVH, D] (any row stride); with block_table they are
@@ -195,7 +195,17 @@ def flash_attn_varlen_func(q, k, v, max_seqlen_q, cu_seqlens_q, max_seqlen_k, cu
     11 bits; a V value that does not fit fp16 makes the kernel itself fall back to the exact form, no host read).  None (default) = where it pays and
     is invisible: the library decides (nvh_plan_prefill with NVH_PV_AUTO; the rule is csrc/plan.h's), this function only asks; True = always
     (no block_table); False = never (P as bf16 hi + lo, 6e-6).  Error of the fp16 form <= 2^-12 * max|v|: 4.5e-4 on the reference goldens (the
-    reference's flash backend rounds P to a single bf16, 8 bits).  DESIGN.md section 12.2."""
+    reference's flash backend rounds P to a single bf16, 8 bits).  DESIGN.md section 12.2.
+    key_splits: the split-key form (nvh_prefill_varlen_splitk) for short query chunks over a long cached prefix: None (default) = today's call,
+    "auto" = the library's rule (csrc/plan.h; one split is exactly today's exact-P V launch), an int = that many workgroups per 64-row query tile
+    (clamped to the key tiles).  Exact P V only: not with kernel=, short_waves or pv_fp16=True.  The hand-off workspace is the per-device
+    zero-filled buffer of reserve_workspace(kind="prefill_splitk"): one such call at a time per device."""
+    if key_splits is not None:
+        if kernel is not None or short_waves or pv_fp16:
+            raise ValueError("key_splits goes with the default kernel choice and exact P V (no kernel=, short_waves or pv_fp16=True)")
+        if key_splits != "auto" and (isinstance(key_splits, bool) or not isinstance(key_splits, int) or key_splits < 1):
+            raise ValueError(f"key_splits must be None, 'auto' or a positive int, got {key_splits!r}")
+        pv_fp16 = False
     if kernel is not None or short_waves or block_table is not None:
         assert not pv_fp16 or kernel == "tiled_f16v", "pv_fp16 goes with the default kernel choice and packed k / v rows"
         pv_fp16 = False
@@ -232,6 +242,13 @@ def flash_attn_varlen_func(q, k, v, max_seqlen_q, cu_seqlens_q, max_seqlen_k, cu
             int(max_seqlen_q), int(max_seqlen_k), h, kvh, hd, bs, max_blocks, q.stride(0), k_stride, v_stride, bt_stride,
             float(softmax_scale), NVH_BF16, _out_code(out.dtype), _stream())
     lib = _lib.load()
+    if key_splits is not None:
+        forced = 0 if key_splits == "auto" else int(key_splits)
+        need = int(lib.nvh_prefill_splitk_workspace(batch, int(max_seqlen_q), int(max_seqlen_k), h, hd, forced, 0))
+        ws = reserve_workspace(q.device, need, "prefill_splitk") if need else None
+        rc = lib.nvh_prefill_varlen_splitk(*tail, forced, ws.data_ptr() if need else None, ws.numel() if need else 0)
+        _lib.check(rc, "nvh_prefill_varlen_splitk")
+        return out
     plan = _lib.PrefillPlan()
     rc = lib.nvh_plan_prefill(ctypes.byref(plan), _lib.PREFILL_KERNELS[kernel or "auto"], int(short_waves),
                               _lib.PV_AUTO if pv_fp16 is None else _lib.PV_ALWAYS if pv_fp16 else _lib.PV_NEVER, _out_code(out.dtype),

@@ -30,7 +30,7 @@ def rows():
         ck = torch.arange(0, n_seq * mk + 1, mk, dtype=torch.int32).cuda()
         return lambda: ops.flash_attn_varlen_func(q, k, v, mq, cq, mk, ck, **kw)
 
-    def paged_prefill(n_seq, mq, mk, H=14, KVH=2, D=64, bs=256):
+    def paged_prefill(n_seq, mq, mk, H=14, KVH=2, D=64, bs=256, **kw):
         per = (mk + bs - 1) // bs
         kc = torch.randn(n_seq * per, bs, KVH, D, generator=gen).bfloat16().cuda()
         vc = torch.randn(n_seq * per, bs, KVH, D, generator=gen).bfloat16().cuda()
@@ -38,7 +38,7 @@ def rows():
         bt = torch.arange(n_seq * per, dtype=torch.int32).view(n_seq, per).cuda()
         cq = torch.arange(0, n_seq * mq + 1, mq, dtype=torch.int32).cuda()
         ck = torch.arange(0, n_seq * mk + 1, mk, dtype=torch.int32).cuda()
-        return lambda: ops.flash_attn_varlen_func(q, kc, vc, mq, cq, mk, ck, block_table=bt)
+        return lambda: ops.flash_attn_varlen_func(q, kc, vc, mq, cq, mk, ck, block_table=bt, **kw)
 
     def decode(B, D, max_blocks=4, H=None, KVH=None, bs=256, **kw):
         H, KVH = H or (14 if D == 64 else 28), KVH or (2 if D == 64 else 4)
@@ -70,6 +70,9 @@ def rows():
         ("prefill m 128 fp16", prefill(2, 128, 128, H=4, D=128, pv_fp16=True)),
         ("prefill m 129 fp16", prefill(2, 129, 129, H=4, D=128, pv_fp16=True)),
         ("prefill n", paged_prefill(2, 300, 600)),
+        ("prefill u auto", paged_prefill(1, 64, 4096, key_splits="auto")),        # split-key form: 8 workgroups per q-tile by the rule
+        ("prefill u forced", paged_prefill(2, 300, 600, key_splits=3)),
+        ("prefill u one", paged_prefill(16, 512, 1024, key_splits="auto")),       # the unsplit grid fills the chip: row n's kernel
         ("prefill p", prefill(1, 128, 128, kernel="short")),
         ("prefill r", prefill(64, 128, 128, kernel="tiled_f16v", v_f16=True)),
         ("prefill s 2047", prefill(1, 2047, 2047, H=2, KVH=1, kernel="tiled_f16v", v_f16=True)),

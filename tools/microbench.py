@@ -87,6 +87,8 @@ def main():
     ap.add_argument("--variant", default=None, help="decode: chunked | chunked_p64 | chunked_p128 | chunked_p256 | split_mfma | split_valu (nvh_paged_decode_variant); prefill: auto | tiled | short | tiled_f16v")
     ap.add_argument("--waves", type=int, default=0, help="decode (chunked, D=64): 4 or 8 waves; prefill short kernel: 8 or 16")
     ap.add_argument("--chunks", type=int, default=0, help="decode (chunked): workgroups per (sequence, kv head)")
+    ap.add_argument("--key-splits", default=None, help="prefill --paged: workgroups per 64-row query tile (ops.flash_attn_varlen_func key_splits): auto or a count; "
+                                                       "default: the unsplit call.  With --graph: 8 calls per replayed graph")
     args = ap.parse_args()
     dev = "cuda"
     torch.manual_seed(0)
@@ -148,9 +150,19 @@ def main():
             rows = (torch.arange(b, device=dev)[:, None] * s + torch.arange(s - ql, s, device=dev)[None, :]).reshape(-1)
             qp = qkv[rows][:, :h * d].contiguous().view(b * ql, h, d)
             cuq = torch.arange(0, b * ql + 1, ql, dtype=torch.int32, device=dev)
-            us = time_loop(lambda l: ops.flash_attn_varlen_func(qp, kc, vc, ql, cuq, s, cu, block_table=perm), 1, args.iters, args.warmup)
+            ks = None if args.key_splits is None else args.key_splits if args.key_splits == "auto" else int(args.key_splits)
+            call = lambda l=0: ops.flash_attn_varlen_func(qp, kc, vc, ql, cuq, s, cu, block_table=perm, key_splits=ks)
+            if args.graph:                                       # no host time between the launches: a short chunk's kernel is shorter than the call's host side
+                call(); torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for _ in range(8):
+                        call()
+                us = time_loop(lambda l: g.replay(), 1, args.iters, args.warmup) / 8
+            else:
+                us = time_loop(call, 1, args.iters, args.warmup)
             flops = b * 4 * d * h * (ql * (s - ql) + ql * (ql + 1) / 2)
-            print(json.dumps({"mode": "prefill_paged", "batch": b, "q_len": ql, "k_len": s, "shape": [h, kvh, d], "us_per_call": round(us, 1),
+            print(json.dumps({"mode": "prefill_paged", "graph": args.graph, "key_splits": ks, "batch": b, "q_len": ql, "k_len": s, "shape": [h, kvh, d], "us_per_call": round(us, 2),
                               "TFLOPs": round(flops / us / 1e6, 1), "frac_of_2.5PF": round(flops / us / 1e6 / 2500, 4)}))
             return
         pv = None if args.variant or args.waves else {"auto": None, "fp16": True, "exact": False}[args.pv]
