@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NVH_VERSION 207          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk */
+#define NVH_VERSION 208          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk; 208: nvh_sample_rows / nvh_sample_advance / nvh_gumbel_noise, nvh_linear_desc.sample_* */
 
 /* dtype codes */
 #define NVH_BF16 0
@@ -319,6 +319,24 @@ int nvh_greedy_advance(const void* logits, int n_rows, int n, int64_t logits_row
                        int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
                        const int32_t* block_tables, int64_t bt_row_stride, int block_size,
                        int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps, int dtype, void* stream);
+/*   Temperature sampling (nanovllm/layers/sampler.py: argmax(softmax(logits / T) / Exp(1)) per row) as an arg-max of perturbed
+ *   scores: out[i] = argmax_j (x[i, j] + T_i * g), g = -ln(-ln u) standard Gumbel, which is the same distribution without a softmax
+ *   or a division, and the greedy token bit for bit where T_i <= 0 (or NaN).  The noise is counter-based (csrc/sample_noise.h):
+ *   Philox4x32-10 with key (seed_lo, seed_hi) and counter (j >> 2, row_keys[i], step_lo, step_hi), column j taking output word j & 3;
+ *   u = ((bits >> 9) + 0.5) * 2^-23; score = fma(T, g, x).  A token is therefore a pure function of (logits row, T, seed, row key,
+ *   step, column order): the same on every rank, in every batch composition, on every graph replay.
+ *   nvh_sample_rows     x [n_rows, n] bf16 as nvh_argmax_rows; temperatures float [n_rows]; row_keys uint32 [n_rows]; steps int64
+ *                       [n_rows] (read as uint64)
+ *   nvh_sample_advance  nvh_greedy_advance with that choice of token; the step of row r is row_steps[r] BEFORE this call increments it
+ *   nvh_gumbel_noise    out[j] = g of column j, j < n, for one (seed, row_key, step): the generator alone, for tests */
+int nvh_sample_rows(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                    const float* temperatures, const uint32_t* row_keys, const int64_t* steps, uint64_t seed, int dtype, void* stream);
+int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                       int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
+                       const int32_t* block_tables, int64_t bt_row_stride, int block_size,
+                       int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
+                       const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream);
+int nvh_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, void* stream);
 
 /*
  * Engine widening: weight-streaming linear layer for decode-sized batches, out = x . W^T (+ bias), m <= 64 rows.
@@ -393,6 +411,14 @@ typedef struct nvh_linear_desc {
        read, NULL / 0 = none; ranges above 4 MiB are ignored (large prefetches cost the launch more than they save). */
     const void* prefetch;
     size_t prefetch_bytes;
+    /* sampled candidates (with candidate_val on the NONE epilogue only; all NULL / 0 = none): candidate_val then carries each
+       workgroup's best PERTURBED score x + T * g of nvh_sample_rows (row i: sample_temperatures[i], sample_row_keys[i],
+       sample_steps[i]; in a decode session sample_steps is the row_steps the advance call increments), so that
+       nvh_greedy_advance_candidates[_embed], unchanged, picks the sampled token and the logits are still never written */
+    const float* sample_temperatures;
+    const uint32_t* sample_row_keys;
+    const int64_t* sample_steps;
+    uint64_t sample_seed;
 } nvh_linear_desc;
 int nvh_linear_small_m_ex(const nvh_linear_desc* desc, int dtype, void* stream);
 /* residual[n_rows, hidden] += y (bf16, one rounding — the add of add_rms_forward, layers/layernorm.py:35-36) and, if `packed` is

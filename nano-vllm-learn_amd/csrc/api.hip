@@ -506,6 +506,42 @@ int nvh_greedy_advance(const void* logits, int n_rows, int n, int64_t logits_row
     return launch_argmax_rows(nullptr, logits, n_rows, n, logits_row_stride, adv, (hipStream_t)stream);
 }
 
+static int sample_rows_impl(const char* fn, int64_t* out, const void* logits, int n_rows, int n, int64_t stride, const SampleArgs& s, const AdvanceArgs& adv,
+                            int dtype, void* stream) {
+    if (dtype != NVH_BF16) { set_error("%s: dtype %d unsupported (bf16 only)", fn, dtype); return NVH_E_DTYPE; }
+    if (!logits || !s.temperatures || !s.row_keys || (!s.steps && !adv.row_steps)) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
+    if (n_rows < 0 || n <= 0) { set_error("%s: bad shape", fn); return NVH_E_SHAPE; }
+    if (stride % 8 || stride < n) { set_error("%s: logits row stride must be a multiple of 8 and >= n", fn); return NVH_E_STRIDE; }
+    if (!aligned16(logits)) { set_error("%s: logits must be 16-byte aligned", fn); return NVH_E_ALIGN; }
+    return launch_sample_rows(out, logits, n_rows, n, stride, s, adv, (hipStream_t)stream);
+}
+
+int nvh_sample_rows(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                    const float* temperatures, const uint32_t* row_keys, const int64_t* steps, uint64_t seed, int dtype, void* stream) {
+    if (n_rows == 0) return 0;
+    if (!out || !steps) { set_error("sample_rows: null pointer"); return NVH_E_NULL; }
+    return sample_rows_impl("sample_rows", out, logits, n_rows, n, logits_row_stride, SampleArgs{temperatures, row_keys, steps, seed}, AdvanceArgs{}, dtype, stream);
+}
+
+int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                       int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
+                       const int32_t* block_tables, int64_t bt_row_stride, int block_size,
+                       int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
+                       const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream) {
+    if (n_rows == 0) return 0;
+    if (!input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps) { set_error("sample_advance: null pointer"); return NVH_E_NULL; }
+    if (block_size <= 0 || log_row_stride < n_rows) { set_error("sample_advance: bad shape"); return NVH_E_SHAPE; }
+    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
+    return sample_rows_impl("sample_advance", nullptr, logits, n_rows, n, logits_row_stride, SampleArgs{temperatures, row_keys, nullptr, seed}, adv, dtype, stream);
+}
+
+int nvh_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, void* stream) {
+    if (n == 0) return 0;
+    if (!out) { set_error("gumbel_noise: null pointer"); return NVH_E_NULL; }
+    if (n < 0) { set_error("gumbel_noise: n %d", n); return NVH_E_SHAPE; }
+    return launch_gumbel_noise(out, seed, row_key, step, n, (hipStream_t)stream);
+}
+
 int nvh_linear_small_m(void* out, const void* x, const void* w, const void* bias, int m, int n, int k, int silu_inter,
                        int64_t x_row_stride, int64_t out_row_stride, int dtype, void* stream) {
     if (m == 0) return 0;
@@ -574,6 +610,12 @@ static int linear_args(LinearArgs& a, const nvh_linear_desc* d, int dtype) {
     a.x_packed = d->x_packed; a.out_packed = (uint16_t*)d->out_packed; a.ws_raw = d->workspace; a.ws_bytes = d->workspace_bytes;
     a.ws = nullptr; a.counters = nullptr; a.ksplit = 1; a.tiles = 0;
     a.cand_val = d->candidate_val; a.cand_idx = d->candidate_idx; a.cand_stride = d->candidate_stride;
+    a.smp = SampleArgs{};
+    if (d->sample_temperatures || d->sample_row_keys || d->sample_steps || d->sample_seed) {
+        if (!d->sample_temperatures || !d->sample_row_keys || !d->sample_steps) { set_error("linear_small_m_ex: sample_temperatures / sample_row_keys / sample_steps come together"); return NVH_E_NULL; }
+        if (!d->candidate_val || d->epilogue != NVH_EPI_NONE) { set_error("linear_small_m_ex: the sampling fields need candidates on the NONE epilogue"); return NVH_E_SHAPE; }
+        a.smp = SampleArgs{d->sample_temperatures, d->sample_row_keys, d->sample_steps, d->sample_seed};
+    }
     // prefetch hint: whole 128-byte lines inside [prefetch, prefetch + prefetch_bytes) only (reads never leave the caller's range)
     // Ranges above 4 MiB are ignored: the hint pays for operands whose FIRST-BYTE latency dominates their consumer (a few MB read by a
     // few dozen workgroups); 8.7 and 17.4 MB ranges measured +-0 and +1.3 % on the decode step (the prefetching workgroups outlive the launch)

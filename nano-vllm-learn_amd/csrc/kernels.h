@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "plan.h"
+#include "sample_noise.h"
 
 namespace nvh {
 
@@ -98,7 +99,26 @@ struct AdvanceArgs {             // all null: plain argmax
     int64_t hidden_stride;
     uint16_t* hidden_packed;     // nullable
 };
+#ifdef __HIPCC__
+// scheduler.postprocess (append the token) + prepare_decode for the NEXT step (engine/model_runner.py:244-269), on the device:
+// the row's workgroup owns the row's metadata, so there is nothing to synchronise
+__device__ __forceinline__ void advance_row(const AdvanceArgs& adv, int row, int token) {
+    const int ctx = adv.context_lens[row];
+    if (ctx > 0) {                                             // padding rows (ctx 0, slot -1) stay as they are
+        adv.tokens_log[adv.row_steps[row] * adv.log_stride + row] = token;
+        adv.row_steps[row] += 1;
+        adv.input_ids[row] = token;
+        adv.positions[row] += 1;
+        adv.context_lens[row] = ctx + 1;
+        const int last = ctx;                                  // index of the token the next step stores: new_ctx - 1
+        adv.slot_mapping[row] = adv.block_tables[row * adv.bt_stride + last / adv.block_size] * adv.block_size + last % adv.block_size;
+    }
+}
+#endif
 int launch_argmax_rows(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const AdvanceArgs& adv, hipStream_t stream);
+// sample.hip: temperature sampling of materialised logits (s.steps null: the counter is adv.row_steps) and the bare noise
+int launch_sample_rows(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const SampleArgs& s, const AdvanceArgs& adv, hipStream_t stream);
+int launch_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, hipStream_t stream);
 int launch_argmax_candidates(const float* cand_val, const int32_t* cand_idx, int groups, int64_t cand_stride, int n_rows, int vocab,
                              const AdvanceArgs& adv, hipStream_t stream);   // vocab: chosen indices are clamped to [0, vocab)
 int linear_stream_candidate_groups(int n, int k);   // workgroups (= candidate records per row) of a NONE launch, 0 if unsupported
@@ -136,6 +156,7 @@ struct LinearArgs {
     float* cand_val;             // NONE only, nullable: greedy candidates instead of (or besides) the outputs: every workgroup
     int32_t* cand_idx;           // writes, per row, the largest bf16 output of its columns and that column's index:
     int64_t cand_stride;         // cand_*[workgroup * cand_stride + row]; ties -> lowest column (lm_head + argmax in one pass)
+    SampleArgs smp;              // with candidates only, temperatures null = none: cand_val carries the perturbed scores of sample_noise.h
     const void* pf_ptr;          // nullable: bytes a LATER launch will stream (its weights): the CUs this launch leaves idle read them
     int64_t pf_bytes;            // once (default cache policy), so that the later launch finds them in the memory-side cache
     // the same for the FIRST K/V images of the decode attention launch that follows a ROPE projection (nvh_qkv_rope_attend mode 3): the

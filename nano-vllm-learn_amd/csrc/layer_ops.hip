@@ -126,21 +126,6 @@ __global__ __launch_bounds__(256) void residual_add_pack_kernel(uint16_t* __rest
 
 // Greedy sampling: argmax over each row of bf16 logits (nanovllm/layers/sampler.py at temperature 0 reduces to this).
 // One 1024-thread workgroup per row streams the row with 16-byte loads; ties resolve to the lowest index.
-// scheduler.postprocess (append the token) + prepare_decode for the NEXT step (engine/model_runner.py:244-269), on the device:
-// the row's workgroup owns the row's metadata, so there is nothing to synchronise
-__device__ __forceinline__ void advance_row(const AdvanceArgs& adv, int row, int token) {
-    const int ctx = adv.context_lens[row];
-    if (ctx > 0) {                                             // padding rows (ctx 0, slot -1) stay as they are
-        adv.tokens_log[adv.row_steps[row] * adv.log_stride + row] = token;
-        adv.row_steps[row] += 1;
-        adv.input_ids[row] = token;
-        adv.positions[row] += 1;
-        adv.context_lens[row] = ctx + 1;
-        const int last = ctx;                                  // index of the token the next step stores: new_ctx - 1
-        adv.slot_mapping[row] = adv.block_tables[row * adv.bt_stride + last / adv.block_size] * adv.block_size + last % adv.block_size;
-    }
-}
-
 // Final step of the fused lm_head + argmax: per row, the best of `groups` candidates (value desc, column asc), then the
 // advance bookkeeping.  One 256-thread workgroup per row.
 __global__ __launch_bounds__(256) void argmax_candidates_kernel(const float* __restrict__ cand_val, const int32_t* __restrict__ cand_idx,

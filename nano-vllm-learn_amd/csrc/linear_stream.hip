@@ -18,7 +18,9 @@
 //     is in flight.
 //   * wide N (LM head): a workgroup walks several tiles with x held in registers and the next tile's W DMA in flight
 //     (MULTI), so x is fetched once per workgroup instead of once per tile; with candidate buffers it also keeps the
-//     running arg-max of its columns, so a greedy decode step never writes the logits.
+//     running arg-max of its columns, so a greedy decode step never writes the logits.  SAMPLE: the same candidates over the
+//     PERTURBED scores l + T g of sample_noise.h (temperature sampling is an arg-max too), a separate instantiation; the Philox
+//     and logarithm work of a tile is done between the issue of the NEXT tile's weight DMA and the wait for this tile's.
 //   * WAVES: 8 per workgroup by default (two per SIMD, half the pieces each): a wave spends most of its life ISSUING (24 DMA +
 //     16 x loads on gate_up ~ 2.8 us at one wave per SIMD) and two waves per SIMD overlap those phases: decode step -4.7 %
 //     (same-box A/B, NVH_GEMM_WAVES=4 restores the old shape).  The multi-tile LM head (two workgroups per CU) stays at 4.
@@ -164,7 +166,7 @@ __device__ __forceinline__ void prefetch_kv_images(const LinearArgs::KvPrefetch&
 // kernarg round trip (14 dwords = the preload count of build.py)
 #define LS_FLAT(a) (a).w, (a).x, (a).K, (a).N, (a).ksplit, (a).tiles, ((a).epi == EPI_RESADD ? (a).M : (a).inter),       \
                    ((a).epi == EPI_RESADD ? (int)(a).out_stride : (a).hd), ((a).K / 64) / (a).ksplit, ((a).K / 64) % (a).ksplit, (a).out, (a)
-template <int MT, int EPI, int NORM, bool XPACK, bool MULTI, int PM = 4, bool WIDE = false, int NWV = 4>
+template <int MT, int EPI, int NORM, bool XPACK, bool MULTI, int PM = 4, bool WIDE = false, int NWV = 4, bool SAMPLE = false>
 __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
     // what the first W DMA and the x loads need comes first and flat: with -amdgpu-kernarg-preload-count these are in SGPRs when the
     // wave starts instead of behind a kernarg s_load (build.py); the rest of the descriptor follows by reference
@@ -174,6 +176,7 @@ __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
     constexpr int TPB = NWV * 64;                                              // threads per workgroup
     constexpr int EPT = (MT * 256 + TPB - 1) / TPB;                            // output element slots per thread
     static_assert(!WIDE || (EPI == EPI_SILU && !MULTI), "wide tiles: SiLU gate_up, one tile per workgroup");
+    static_assert(!SAMPLE || EPI == EPI_NONE, "sampled candidates: the plain epilogue (the LM head)");
     constexpr int PMAX = PM;
     constexpr int NB = WIDE ? 4 : (EPI == EPI_SILU || EPI == EPI_ROPE) ? 2 : 1;   // weight row blocks per tile
     constexpr int NBUF = MULTI ? 2 : 1;
@@ -340,6 +343,24 @@ __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
     uint16_t* const e_k_cache = a.k_cache;
     uint16_t* const e_v_cache = a.v_cache;
     asm volatile("" ::"s"(e_out), "s"(e_out_packed), "s"(e_out_stride), "s"(e_ws), "s"(e_counters), "s"(e_norm_eps), "s"(e_k_cache), "s"(e_v_cache));
+    // SAMPLE: an element slot is the same row in every tile, so its temperature, row key and noise step are fetched once, here
+    // (rows past M read row M - 1: in bounds, never used)
+    float sm_t[EPT], sm_g[EPT];
+    uint32_t sm_key[EPT], sm_slo[EPT], sm_shi[EPT];
+    const uint64_t sm_seed = a.smp.seed;
+    if constexpr (SAMPLE) {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            const int v = tid + TPB * j, l = (v >> 2) & 63;
+            const int row = min(16 * (v >> 8) + 4 * (l >> 4) + (v & 3), a.M - 1);
+            const uint64_t st = (uint64_t)a.smp.steps[row];
+            sm_t[j] = a.smp.temperatures[row];
+            sm_key[j] = a.smp.row_keys[row];
+            sm_slo[j] = (uint32_t)st;
+            sm_shi[j] = (uint32_t)(st >> 32);
+            sm_g[j] = 0.f;
+        }
+    }
 
     float ss2[MT];
 #pragma unroll
@@ -361,10 +382,24 @@ __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
         for (int i = 0; i < 2 * PMAX; ++i)
 #pragma unroll
             for (int m = 0; m < MT; ++m) asm volatile("" : "+v"(araw[i][m]));
+        if constexpr (SAMPLE) {                                  // the same for the sampling operands: landed, plain registers from here on
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) asm volatile("" : "+v"(sm_t[j]), "+v"(sm_key[j]), "+v"(sm_slo[j]), "+v"(sm_shi[j]));
+        }
     }
     for (int tile = tile_first, buf = 0; tile < tile_end; ++tile, buf ^= (NBUF - 1)) {
+        if (MULTI && tile + 1 < tile_end) issue_w(tile + 1, buf ^ 1);
+        if constexpr (SAMPLE) {
+            // this tile's Gumbel draws (a thread owns column lane / 4 % 16 of the tile in every slot): pure VALU work that needs nothing from
+            // memory, placed where the wave would otherwise sit in the wait below; the pin keeps it in front of that wait
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) {
+                if (sm_t[j] > 0.f)
+                    sm_g[j] = sample_gumbel(sm_seed, sm_key[j], ((uint64_t)sm_shi[j] << 32) | sm_slo[j], (uint32_t)(tile * 16 + ((tid >> 2) & 15)));
+                asm volatile("" : "+v"(sm_g[j]));
+            }
+        }
         if (MULTI && tile + 1 < tile_end) {
-            issue_w(tile + 1, buf ^ 1);
             wait_all_but_pieces<NB * 2>(np);
         } else {
             // RoPE epilogue: the cos / sin loads hang on positions[row] and are therefore issued last, a round trip behind everything
@@ -583,8 +618,10 @@ __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
                 const __bf16 o = (__bf16)(y[0] + (a.bias ? (float)__builtin_bit_cast(__bf16, a.bias[n0 + c]) : 0.f));
                 if (out) out[(int64_t)row * e_out_stride + n0 + c] = o;
                 if (e_out_packed) e_out_packed[pack_index(row, n0 + c, p_N)] = __builtin_bit_cast(uint16_t, o);
-                if (a.cand_val && argmax_better((float)o, n0 + c, best_v[j], best_i[j])) {   // torch.argmax order (NaN first, lowest column on ties)
-                    best_v[j] = (float)o;
+                float score = (float)o;
+                if constexpr (SAMPLE) score = sample_score(score, sm_t[j], sm_g[j]);
+                if (a.cand_val && argmax_better(score, n0 + c, best_v[j], best_i[j])) {   // torch.argmax order (NaN first, lowest column on ties)
+                    best_v[j] = score;
                     best_i[j] = n0 + c;
                 }
             }
@@ -631,6 +668,13 @@ template <int MT, int EPI, int NORM, bool XPACK>
 int launch_x(const LinearArgs& a_in, hipStream_t stream) {
     LinearArgs a = a_in;
     const bool multi = EPI == EPI_NONE && a.ksplit == 1 && a.tiles > 1024;
+    if constexpr (EPI == EPI_NONE) {
+        if (a.smp.temperatures) {                                    // sampled candidates (ksplit == 1: launch_linear_stream): the two shapes a candidates launch takes
+            if (multi) hipLaunchKernelGGL((linear_stream_kernel<MT, EPI, NORM, XPACK, true, 4, false, 4, true>), dim3(kMultiWgs), dim3(SW * 64), 0, stream, LS_FLAT(a));
+            else hipLaunchKernelGGL((linear_stream_kernel<MT, EPI, NORM, XPACK, false, 2, false, 8, true>), grid_of(a), dim3(8 * 64), 0, stream, LS_FLAT(a));
+            return check_launch("linear_stream");
+        }
+    }
     if (multi) {
         if constexpr (EPI == EPI_NONE) {
             // (eight waves per workgroup measured slower here: 72 vs 49 us for the LM head)
@@ -715,6 +759,7 @@ int launch_linear_stream(const LinearArgs& a_in, hipStream_t stream) {
     if (a.M == 0) return 0;
     if (a.norm_mode == 1 || a.K % 64 != 0 || a.M > 64) return -100;
     if (a.cand_val && (a.epi != EPI_NONE || !a.cand_idx || linear_stream_candidate_groups(a.N, a.K) == 0)) return -100;
+    if (a.smp.temperatures && !a.cand_val) return -100;
     a.tiles = tiles_of(a.N, a.inter, a.h, a.kvh, a.hd, a.epi);
     const int pieces = a.K / 64;
     a.ksplit = (pieces + SW * PMAX - 1) / (SW * PMAX);

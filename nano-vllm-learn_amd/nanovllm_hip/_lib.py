@@ -27,7 +27,9 @@ class LinearDesc(ctypes.Structure):
                 ("norm_folded", ctypes.c_int32), ("x_packed", ctypes.c_int32), ("out_packed", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
                 ("candidate_val", ctypes.c_void_p), ("candidate_idx", ctypes.c_void_p), ("candidate_stride", ctypes.c_int64),
-                ("prefetch", ctypes.c_void_p), ("prefetch_bytes", ctypes.c_size_t)]
+                ("prefetch", ctypes.c_void_p), ("prefetch_bytes", ctypes.c_size_t),
+                ("sample_temperatures", ctypes.c_void_p), ("sample_row_keys", ctypes.c_void_p), ("sample_steps", ctypes.c_void_p),
+                ("sample_seed", ctypes.c_uint64)]
 
 
 class PrefillPlan(ctypes.Structure):
@@ -91,6 +93,12 @@ _SIGS = {
     "nvh_argmax_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "nvh_greedy_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
                            [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_sample_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 3 +
+                        [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_sample_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
+                           [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                            ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_gumbel_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
     "nvh_linear_small_m_ex": (ctypes.c_int, [ctypes.POINTER(LinearDesc), ctypes.c_int, ctypes.c_void_p]),
     "nvh_linear_small_m_workspace": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "nvh_qkv_rope_attend": (ctypes.c_int, [ctypes.POINTER(LinearDesc), ctypes.c_void_p, ctypes.c_void_p, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int,

@@ -1,8 +1,9 @@
 """Minimal generate() loop with the reference's scheduling rules that shape attention inputs
 (nanovllm/engine/scheduler.py:27-89, llm_engine.py:94-143): prefill first, FCFS, a prefill batch holds at most
 max_num_batched_tokens tokens and max_num_seqs sequences; then all running sequences decode together.
-Greedy sampling only (bench_my.py uses temperature 0, ignore_eos, fixed max_tokens), so control flow is
-value-independent and the decode phase runs as a device-resident graph session."""
+Fixed max_tokens and ignore_eos as bench_my.py, so control flow is value-independent and the decode phase runs as a
+device-resident graph session: greedy at temperature 0 (bench_my.py's setting), temperature sampling on the device otherwise
+(DESIGN.md section 14)."""
 from __future__ import annotations
 
 import torch
@@ -40,9 +41,12 @@ class LLMEngine:
             for s, t in zip(batch, self.runner.run(batch, True)):
                 s.append_token(t)
 
-    def generate(self, prompt_token_ids, max_tokens):
-        """Greedy-generate `max_tokens` tokens for every prompt; returns the completion token ids."""
-        seqs = [Sequence(p, max_tokens=max_tokens) for p in prompt_token_ids]
+    def generate(self, prompt_token_ids, max_tokens, temperature=0.0):
+        """Generate `max_tokens` tokens for every prompt; returns the completion token ids.  temperature: one value or one per
+        prompt; 0 = greedy, > 0 = sampled as the reference's sampler.py does (noise seed: ModelConfig.seed)."""
+        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * len(prompt_token_ids)
+        assert len(temps) == len(prompt_token_ids) and all(t >= 0 for t in temps)
+        seqs = [Sequence(p, max_tokens=max_tokens, temperature=t) for p, t in zip(prompt_token_ids, temps)]
         self.prefill(seqs, reserve_tokens=max_tokens)
         if max_tokens > 1:
             if self.enforce_eager:

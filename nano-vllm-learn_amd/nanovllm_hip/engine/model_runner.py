@@ -35,6 +35,17 @@ def greedy_tokens(logits):
     return logits.argmax(dim=-1)
 
 
+def sampling_inputs(seqs, device, steps=None):
+    """What the sampling kernels read per row, or None when every request is greedy (the launches are then the greedy ones):
+    temperatures float32 [b], row keys uint32 [b] (the sequence ids: the noise of a request does not depend on the batch it
+    shares) and, with `steps`, the noise counters int64 [b]."""
+    temps = [float(s.temperature) for s in seqs]
+    if not any(t > 0 for t in temps):
+        return None
+    out = (torch.tensor(temps, dtype=torch.float32).to(device), torch.tensor([s.seq_id & 0xFFFFFFFF for s in seqs], dtype=torch.uint32).to(device))
+    return out if steps is None else out + (torch.tensor(steps, dtype=torch.int64).to(device),)
+
+
 def build_block_tables(seqs, width=None, pad=-1):
     width = width or max(len(s.block_table) for s in seqs)
     rows = [s.block_table + [pad] * (width - len(s.block_table)) for s in seqs]
@@ -134,7 +145,10 @@ class ModelRunner:
 
     @torch.inference_mode()
     def run(self, seqs, is_prefill):
-        """One eager forward (prefill, or a decode step with host-built metadata); returns greedy token ids."""
+        """One eager forward (prefill, or a decode step with host-built metadata); returns the next token ids: greedy, or sampled
+        (ops.sample_rows) where a sequence's temperature is positive.  The noise counter of a decode step is the one a DecodeSession
+        started after the prefill would use (completion tokens so far - 1), so eager and graph generation draw the same tokens;
+        the prefill's own token takes the counter in front of that, -1 (2^64 - 1 as the kernels read it)."""
         m = build_prefill_meta(seqs, self.block_size) if is_prefill else build_decode_meta(seqs, self.block_size)
         if is_prefill:
             slots = m["slot_mapping"] if m["slot_mapping"].numel() else None          # warmup: nothing to store
@@ -147,7 +161,9 @@ class ModelRunner:
         if is_prefill:
             last = self._dev(m["cu_seqlens_q"])[1:].long() - 1                     # last token of every sequence (embed_head.py:62-65)
             hidden = hidden[last]
-        tokens = greedy_tokens(self.model.compute_logits(hidden))
+        logits = self.model.compute_logits(hidden)
+        smp = sampling_inputs(seqs, self.device, steps=[s.num_completion_tokens - 1 for s in seqs])
+        tokens = greedy_tokens(logits) if smp is None else ops.sample_rows(logits, *smp, self.cfg.seed)
         reset_context()
         out = tokens.tolist()                                                         # (the host synchronises here anyway)
         self.raise_if_device_failed()
@@ -195,7 +211,7 @@ def _force_end_capture(stream):
 
 
 class DecodeSession:
-    """Batched greedy decode of `seqs` for a fixed number of steps with device-resident metadata.
+    """Batched decode of `seqs` (greedy, or sampled where Sequence.temperature > 0) for a fixed number of steps with device-resident metadata.
 
     All blocks the sequences will need are already in their block tables (BlockManager.allocate(reserve_tokens=...)),
     so block tables are static; per step the device advances input_ids / positions / context_lens / slot_mapping
@@ -226,6 +242,10 @@ class DecodeSession:
         self.row_steps = torch.zeros(b, dtype=torch.int64, device=dev)          # tokens generated per row (device-side log index)
         self.max_new_tokens = max_new_tokens
         self.steps_done = 0
+        # temperature sampling: the noise counter is row_steps itself, which the advance launch increments inside the graph
+        self.sampling = sampling_inputs(seqs, dev)
+        if self.sampling is not None:
+            self.sampling += (self.row_steps, runner.cfg.seed)
         cfg = runner.cfg
         h = tp_partition(cfg.num_attention_heads, cfg.num_key_value_heads, runner.world_size, runner.rank)[1]
         ops.reserve_workspace(dev, ops.decode_workspace_bytes(b, h, cfg.head_dim, self.block_tables.shape[1], bs))
@@ -281,7 +301,7 @@ class DecodeSession:
             hidden = model(self.input_ids, self.positions, embedded=(self.hidden_in, self.hidden_in_p))
         else:
             hidden = model(self.input_ids, self.positions)
-        cand = model.greedy_candidates(hidden)                 # LM head + arg-max candidates in one launch (fused decode path)
+        cand = model.greedy_candidates(hidden, sampling=self.sampling)   # LM head + arg-max candidates in one launch (fused decode path)
         if cand is not None:
             embed = (model.embed_tokens.weight, self.hidden_in, self.hidden_in_p) if self.fuse_embed else None
             ops.greedy_advance_candidates(cand[0], cand[1], cand[2], self.batch, self.input_ids, self.positions, self.context_lens,
@@ -290,7 +310,11 @@ class DecodeSession:
             return
         assert not self.fuse_embed, "the fused embedding needs the candidates path"
         logits = self.runner.model.compute_logits(hidden)
-        if logits.is_cuda and logits.dtype == torch.bfloat16 and logits.stride(0) % 8 == 0:
+        if self.sampling is not None:
+            temps, keys, _, seed = self.sampling
+            ops.sample_advance(logits, self.input_ids, self.positions, self.context_lens, self.slot_mapping, self.block_tables,
+                               self.runner.block_size, self.tokens, self.row_steps, temps, keys, seed)
+        elif logits.is_cuda and logits.dtype == torch.bfloat16 and logits.stride(0) % 8 == 0:
             # sampling + postprocess + next step's prepare_decode in ONE launch (nvh_greedy_advance)
             ops.greedy_advance(logits, self.input_ids, self.positions, self.context_lens, self.slot_mapping, self.block_tables,
                                self.runner.block_size, self.tokens, self.row_steps)

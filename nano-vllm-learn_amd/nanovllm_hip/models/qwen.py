@@ -44,6 +44,7 @@ class ModelConfig:
     max_position_embeddings: int = 32768
     attn_backend: str = "hip"
     kvcache_block_size: int = 256
+    seed: int = 0                            # of the sampling noise (csrc/sample_noise.h); greedy requests never read it
 
 
 # public HF config.json values
@@ -471,10 +472,11 @@ class QwenForCausalLM(nn.Module):
                 and self.embed_tokens.weight.dtype == torch.bfloat16 and self.cfg.hidden_size % 32 == 0 and self._fused_shapes_ok()
                 and ops.linear_candidate_groups(self.cfg.vocab_size, self.cfg.hidden_size) > 0)   # the arg-max must be the candidates launch
 
-    def greedy_candidates(self, hidden_states):
+    def greedy_candidates(self, hidden_states, sampling=None):
         """Fused decode path only: LM head + per-workgroup arg-max candidates in one launch, logits never written.  Returns
         (val [groups, stride] float32, idx int32, groups) for ops.greedy_advance_candidates, or None when this path does not
-        apply (then use compute_logits)."""
+        apply (then use compute_logits).  sampling = (temperatures, row_keys, steps, seed): the candidates of the perturbed
+        scores (ops.fused_linear), i.e. the same call then SAMPLES."""
         if not isinstance(hidden_states, PackedResidual):
             return None
         packed = hidden_states.packed
@@ -489,7 +491,8 @@ class QwenForCausalLM(nn.Module):
         if "cand" not in b:
             b["cand"] = (torch.empty((groups, 64), dtype=torch.float32, device=hidden_states.device),
                          torch.empty((groups, 64), dtype=torch.int32, device=hidden_states.device))
-        ops.fused_linear(packed, head, x_packed_rows=m, norm_folded=True, norm_eps=self.norm.eps, candidates=b["cand"], want_out=False)
+        ops.fused_linear(packed, head, x_packed_rows=m, norm_folded=True, norm_eps=self.norm.eps, candidates=b["cand"], want_out=False,
+                         sampling=sampling)
         return b["cand"][0], b["cand"][1], groups
 
     @torch.no_grad()

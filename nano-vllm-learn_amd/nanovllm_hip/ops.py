@@ -394,7 +394,7 @@ _EPI_CODES = {"none": _lib.EPI_NONE, "silu_mul": _lib.EPI_SILU_MUL, "residual_ad
 
 
 def fused_linear(x, weight, *, bias=None, norm_weight=None, norm_eps=1e-6, norm_folded=False, epilogue="none", out=None, rope=None,
-                 x_packed_rows=None, out_packed=None, workspace=None, want_out=True, candidates=None, prefetch=None):
+                 x_packed_rows=None, out_packed=None, workspace=None, want_out=True, candidates=None, prefetch=None, sampling=None):
     """nvh_linear_small_m_ex: x [M<=64, K] . weight[N, K]^T with an optional RMSNorm prologue and one of the epilogues
     "none" (+bias) | "silu_mul" | "residual_add" (out = the residual stream, updated in place) | "rope_store"
     (rope = dict(positions, cos_sin, k_cache, v_cache, slot_mapping, num_heads, num_kv_heads, head_dim); returns q [M, H*D]).
@@ -405,17 +405,19 @@ def fused_linear(x, weight, *, bias=None, norm_weight=None, norm_eps=1e-6, norm_
     per workgroup and row the best bf16 output and its column ("none" only) — with want_out=False the outputs themselves are
     never written (LM head + greedy arg-max in one pass; finish with greedy_advance_candidates).
     prefetch = a contiguous CUDA tensor the NEXT launch will stream (the following projection's weights): the CUs this launch
-    leaves idle read it into the caches first (a hint; results do not depend on it)."""
+    leaves idle read it into the caches first (a hint; results do not depend on it).
+    sampling = (temperatures float32 [M], row_keys uint32 [M], steps int64 [M], seed) with candidates only: the candidates are taken
+    over the perturbed scores of sample_rows, so that greedy_advance_candidates picks the SAMPLED token (rows with T <= 0: greedy)."""
     d, out = _linear_desc(x, weight, bias=bias, norm_weight=norm_weight, norm_eps=norm_eps, norm_folded=norm_folded, epilogue=epilogue, out=out,
                           rope=rope, x_packed_rows=x_packed_rows, out_packed=out_packed, workspace=workspace, want_out=want_out,
-                          candidates=candidates, prefetch=prefetch)
+                          candidates=candidates, prefetch=prefetch, sampling=sampling)
     rc = _lib.load().nvh_linear_small_m_ex(ctypes.byref(d), NVH_BF16, _stream())
     _lib.check(rc, "nvh_linear_small_m_ex")
     return out
 
 
 def _linear_desc(x, weight, *, bias=None, norm_weight=None, norm_eps=1e-6, norm_folded=False, epilogue="none", out=None, rope=None,
-                 x_packed_rows=None, out_packed=None, workspace=None, want_out=True, candidates=None, prefetch=None):
+                 x_packed_rows=None, out_packed=None, workspace=None, want_out=True, candidates=None, prefetch=None, sampling=None):
     """Build the nvh_linear_desc of fused_linear's arguments; returns (descriptor, out)."""
     _require_gpu_bf16(x=x, weight=weight)
     n, k = weight.shape
@@ -469,6 +471,12 @@ def _linear_desc(x, weight, *, bias=None, norm_weight=None, norm_eps=1e-6, norm_
         assert cv.shape == ci.shape and cv.dim() == 2 and cv.is_contiguous() and ci.is_contiguous()
         assert cv.shape[0] >= linear_candidate_groups(n, k) > 0 and cv.shape[1] >= m
         d.candidate_val, d.candidate_idx, d.candidate_stride = cv.data_ptr(), ci.data_ptr(), cv.stride(0)
+    if sampling is not None:
+        assert candidates is not None, "sampling perturbs the candidates: pass candidates="
+        temperatures, row_keys, steps, seed = sampling
+        _require_sampling(m, temperatures, row_keys, steps)
+        d.sample_temperatures, d.sample_row_keys, d.sample_steps = temperatures.data_ptr(), row_keys.data_ptr(), steps.data_ptr()
+        d.sample_seed = int(seed) & _U64
     if prefetch is not None:
         assert prefetch.is_cuda and prefetch.is_contiguous()
         d.prefetch, d.prefetch_bytes = prefetch.data_ptr(), prefetch.numel() * prefetch.element_size()
@@ -570,6 +578,59 @@ def argmax_rows(logits):
     out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
     rc = _lib.load().nvh_argmax_rows(out.data_ptr(), logits.data_ptr(), logits.shape[0], logits.shape[1], logits.stride(0), NVH_BF16, _stream())
     _lib.check(rc, "nvh_argmax_rows")
+    return out
+
+
+_U64 = (1 << 64) - 1
+
+
+def _require_sampling(m, temperatures, row_keys, steps=None):
+    assert temperatures.is_cuda and temperatures.dtype == torch.float32 and temperatures.numel() == m and temperatures.is_contiguous()
+    assert row_keys.is_cuda and row_keys.dtype in (torch.uint32, torch.int32) and row_keys.numel() == m and row_keys.is_contiguous()
+    if steps is not None:
+        assert steps.is_cuda and steps.dtype == torch.int64 and steps.numel() == m and steps.is_contiguous()
+
+
+def sample_rows(logits, temperatures, row_keys, steps, seed):
+    """Temperature sampling per row of bf16 logits [M, N] (nvh_sample_rows): argmax_j (logits[i, j] + T_i * g) with the counter-based
+    Gumbel noise g(seed, row_keys[i], steps[i], j) of csrc/sample_noise.h — the distribution of the reference's sampler.py, the greedy
+    token where T_i <= 0.  temperatures float32 [M], row_keys uint32 [M], steps int64 [M] (read as uint64).  Returns int64 [M]."""
+    _require_gpu_bf16(logits=logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    m = logits.shape[0]
+    _require_sampling(m, temperatures, row_keys, steps)
+    out = torch.empty(m, dtype=torch.int64, device=logits.device)
+    rc = _lib.load().nvh_sample_rows(out.data_ptr(), logits.data_ptr(), m, logits.shape[1], logits.stride(0), temperatures.data_ptr(),
+                                     row_keys.data_ptr(), steps.data_ptr(), int(seed) & _U64, NVH_BF16, _stream())
+    _lib.check(rc, "nvh_sample_rows")
+    return out
+
+
+def sample_advance(logits, input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps,
+                   temperatures, row_keys, seed):
+    """greedy_advance with sample_rows' choice of token (nvh_sample_advance); the noise step of a row is row_steps[row] before the
+    call increments it, so a captured step draws fresh noise on every replay."""
+    _require_gpu_bf16(logits=logits)
+    _require_i32(context_lens=context_lens, slot_mapping=slot_mapping, block_tables=block_tables)
+    m = logits.shape[0]
+    assert logits.dim() == 2 and logits.stride(1) == 1 and block_tables.stride(1) == 1
+    for t in (input_ids, positions, tokens_log, row_steps):
+        assert t.dtype == torch.int64 and t.is_cuda
+    assert tokens_log.dim() == 2 and tokens_log.shape[1] >= m and tokens_log.stride(1) == 1
+    _require_sampling(m, temperatures, row_keys)
+    rc = _lib.load().nvh_sample_advance(logits.data_ptr(), m, logits.shape[1], logits.stride(0), input_ids.data_ptr(), positions.data_ptr(),
+                                        context_lens.data_ptr(), slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
+                                        block_size, tokens_log.data_ptr(), tokens_log.stride(0), row_steps.data_ptr(), temperatures.data_ptr(),
+                                        row_keys.data_ptr(), int(seed) & _U64, NVH_BF16, _stream())
+    _lib.check(rc, "nvh_sample_advance")
+
+
+def gumbel_noise(seed, row_key, step, n, device="cuda"):
+    """The noise alone: g of columns 0..n-1 for one (seed, row_key, step), float32 [n] (nvh_gumbel_noise)."""
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    with torch.cuda.device(out.device):
+        rc = _lib.load().nvh_gumbel_noise(out.data_ptr(), int(seed) & _U64, int(row_key) & 0xFFFFFFFF, int(step) & _U64, n, _stream())
+    _lib.check(rc, "nvh_gumbel_noise")
     return out
 
 

@@ -6,6 +6,7 @@ cycling over `--layers` distinct KV caches so that no launch re-reads what the p
 256 MiB Infinity Cache, and prints achieved algorithmic GB/s (decode) or TFLOP/s (prefill).
 
     python tools/microbench.py decode --batch 32 --ctx 1536 --heads 14 --kv-heads 2 --head-dim 64
+    python tools/microbench.py lmhead --batch 32 --hidden 896 --vocab 151936     # LM head + advance, greedy against sampled
 """
 import argparse
 import json
@@ -63,9 +64,55 @@ def time_loop(fn, n_layers, iters, warmup):
     return start.elapsed_time(end) * 1e3 / (iters * n_layers)       # us per call
 
 
+def lmhead(args, dev):
+    """The tail of a fused decode step under graph replay: the streaming LM head with candidates + nvh_greedy_advance_candidates_embed,
+    greedy against sampled (temperature 1 in every row), alternating so that both see the same machine.  --layers launches pairs per graph
+    over as many distinct weight copies as fit 2 GiB, so that the weights come from HBM as in a real step."""
+    b, k, n = args.batch, args.hidden, args.vocab
+    groups = ops.linear_candidate_groups(n, k)
+    assert groups > 0, "shape not served by the candidates launch"
+    copies = max(1, min(args.layers, (2 << 30) // (n * k * 2)))
+    ws = [torch.randn(n, k, device=dev, dtype=torch.bfloat16) * 0.05 for _ in range(copies)]
+    xp = ops.pack_rows(torch.randn(b, k, device=dev, dtype=torch.bfloat16))
+    cand = (torch.zeros(groups, 64, dtype=torch.float32, device=dev), torch.zeros(groups, 64, dtype=torch.int32, device=dev))
+    steps_cap = 6 * args.layers * (args.iters + args.warmup) + 64    # every replay advances the rows: 3 repeats x 2 graphs, + the warm-up steps
+    st = dict(input_ids=torch.zeros(b, dtype=torch.int64, device=dev), positions=torch.full((b,), 8, dtype=torch.int64, device=dev),
+              context_lens=torch.full((b,), 8, dtype=torch.int32, device=dev), slot_mapping=torch.zeros(b, dtype=torch.int32, device=dev),
+              block_tables=torch.zeros(b, (steps_cap + 8) // 256 + 2, dtype=torch.int32, device=dev),
+              tokens=torch.zeros(steps_cap, b, dtype=torch.int64, device=dev), row_steps=torch.zeros(b, dtype=torch.int64, device=dev))
+    hid, hid_p = torch.zeros(b, k, dtype=torch.bfloat16, device=dev), torch.zeros(((b + 15) // 16) * 16 * k, dtype=torch.bfloat16, device=dev)
+    sampling = (torch.ones(b, device=dev), torch.arange(b, dtype=torch.int32, device=dev), st["row_steps"], 1)
+
+    def step(l, smp):
+        ops.fused_linear(xp, ws[l % copies], x_packed_rows=b, norm_folded=True, candidates=cand, want_out=False, sampling=smp)
+        ops.greedy_advance_candidates(cand[0], cand[1], groups, b, st["input_ids"], st["positions"], st["context_lens"], st["slot_mapping"],
+                                      st["block_tables"], 256, st["tokens"], st["row_steps"], embed=(ws[0], hid, hid_p))
+
+    graphs = {}
+    for name, smp in (("greedy", None), ("sampled", sampling)):
+        step(0, smp)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for l in range(args.layers):
+                step(l, smp)
+        graphs[name] = g
+    us = {"greedy": [], "sampled": []}
+    for _ in range(3):                                           # alternate: the spread between repeats is the noise floor of the comparison
+        for name, g in graphs.items():
+            us[name].append(time_loop(lambda l: g.replay(), 1, args.iters, args.warmup) / args.layers)
+    assert int(st["row_steps"].max()) < steps_cap
+    gm, sm = min(us["greedy"]), min(us["sampled"])
+    print(json.dumps({"mode": "lmhead", "batch": b, "hidden": k, "vocab": n, "weight_copies": copies, "launches_per_graph": args.layers,
+                      "greedy_us": [round(v, 2) for v in us["greedy"]], "sampled_us": [round(v, 2) for v in us["sampled"]],
+                      "sampled_over_greedy": round(sm / gm, 4), "weight_MB": round(n * k * 2 / 1e6, 1), "greedy_GBps": round(n * k * 2 / gm / 1e3, 1)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["decode", "prefill"])
+    ap.add_argument("mode", choices=["decode", "prefill", "lmhead"])
+    ap.add_argument("--hidden", type=int, default=896, help="lmhead: K")
+    ap.add_argument("--vocab", type=int, default=151936, help="lmhead: N")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--ctx", type=int, default=1536)
     ap.add_argument("--ctx-lo", type=int, default=0, help="if set, context lengths uniform in [ctx-lo, ctx]")
@@ -92,6 +139,8 @@ def main():
     args = ap.parse_args()
     dev = "cuda"
     torch.manual_seed(0)
+    if args.mode == "lmhead":
+        return lmhead(args, dev)
     if args.mode == "decode":
         q, caches, cl, bt, ctxs = make_decode(args, dev)
         b, h, kvh, d = args.batch, args.heads, args.kv_heads, args.head_dim
