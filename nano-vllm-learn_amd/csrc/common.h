@@ -25,6 +25,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef short bf16x8_s __attribute__((ext_vector_type(8)));   // MFMA A/B fragment: 8 bf16 in 4 VGPRs
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // ---- bf16 <-> f32 -----------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_lo(uint32_t packed) { return __uint_as_float(packed << 16); }
@@ -72,6 +75,12 @@ __device__ __forceinline__ float pair_in_row(float x) {
 __device__ __forceinline__ float max2(float x, float y) {
     float r;
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+// one v_max3_f32, for the same reason (MFMA outputs are not known to be quiet)
+__device__ __forceinline__ float max3(float x, float y, float z) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
     return r;
 }
 __device__ __forceinline__ float max_xor16(float x) {
@@ -128,6 +137,36 @@ __device__ __forceinline__ bool argmax_better(float v, int i, float best, int bi
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// ---- LDS images of K / V tiles and their MFMA operand reads --------------------------------------
+// Images are row-major [rows][D bf16], LPT = D / 8 16-byte chunks per row, filled by LDS-DMA; the chunk order inside row `row` is
+// XOR-swizzled on the SOURCE address so that the MFMA operand reads (ds_read_b128 of one chunk per lane) are bank-conflict free.
+template <int LPT>
+__device__ __forceinline__ int chunk_swizzle(int row) {
+    return LPT == 8 ? ((row >> 1) & 7) : (row & 15);
+}
+// The V image has its own swizzle: its transposed reads (ds_read_b64_tr_b16) bank per 32-lane half, where lanes address rows
+// r and r+2 (128-byte rows) / r and r+1 (256-byte rows) on the same banks; with the K swizzle those pairs land on the same
+// chunk pair (2-way conflict on every V read: a third of all LDS cycles, SQ_LDS_BANK_CONFLICT).  Even XOR values that differ
+// for the 4 (8) rows of a bank class make the 32 lanes hit 32 distinct 8-byte slots.  Rows r, r+16, r+32 share a value.
+template <int LPT>
+__device__ __forceinline__ int chunk_swizzle_v(int row) {
+    return LPT == 8 ? (row & 6) : ((2 * row) & 14);
+}
+__device__ __forceinline__ uint32_t lds_offset(const void* p) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
+}
+// ds_read_b64_tr_b16 (hardware transpose of a 4-key x 16-dim block) through inline asm: the builtin form makes hipcc wait vmcnt(0)
+// before the read (it cannot prove the read does not alias the LDS-DMA of the NEXT tile that is still in flight), which serialised the
+// double buffer.  OFF: the instruction's immediate offset.  The caller issues a batch of these, then `s_waitcnt lgkmcnt(0)` + a
+// scheduling fence before the first use.
+template <int OFF = 0>
+__device__ __forceinline__ u32x2 ds_read_tr16_b64_asm(uint32_t lds_addr) {
+    static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
+    u32x2 r;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
+    return r;
+}
 
 // ---- host-side error plumbing ------------------------------------------------------------------
 void set_error(const char* fmt, ...);

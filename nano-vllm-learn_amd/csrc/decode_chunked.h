@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "handoff.h"
 #include "kernels.h"
 
 namespace nvh {
@@ -62,83 +63,15 @@ struct MGeo {
     static constexpr int SPLIT = MW * WT;
 };
 
-// swizzle of the 16-byte chunk position inside row T of an LDS image
-template <int LPT>
-__device__ __forceinline__ int chunk_swizzle(int T) {
-    return LPT == 8 ? ((T >> 1) & 7) : (T & 15);
-}
-
-// V image swizzle of the chunked kernel (see prefill_mfma.hip chunk_swz_v): makes the transposed V reads conflict free
-template <int LPT>
-__device__ __forceinline__ int chunk_swizzle_v(int T) {
-    return LPT == 8 ? (T & 6) : ((2 * T) & 14);
-}
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-// ds_read_b64_tr_b16 through inline asm: with the builtin hipcc waits vmcnt(0) before the read (it cannot prove the read does
-// not alias the LDS-DMA of the NEXT pass still in flight).  The caller batches these, then `s_waitcnt lgkmcnt(0)` + a
-// scheduling fence before the first use.
-__device__ __forceinline__ u32x2 ds_read_tr16_b64_asm(uint32_t lds_addr) {
-    u32x2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(lds_addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ uint32_t lds_offset(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-// one v_max3_f32: plain fmaxf on MFMA outputs makes hipcc emit a canonicalising v_max x,x before every use
-__device__ __forceinline__ float max3(float x, float y, float z) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
-    return r;
-}
-
 // wave-uniform int32 load through the constant address space: stays a scalar load (lgkmcnt) inside loops that also hold
 // stores and LDS-DMA, where a plain load would be a vector load whose vmcnt wait drains the DMA queue
 __device__ __forceinline__ int32_t load_uniform_i32(const int32_t* p) {
     return *(const __attribute__((address_space(4))) int32_t*)(uintptr_t)p;
 }
 
-// The chunk hand-off's two flavours.  Default: the records move as write-through stores / L1-bypassing loads (sc1) and no fence is
-// needed.  -DNVH_HANDOFF_FENCES (cross-check build, never shipped; tools/probes/run_fence_crosscheck.sh): the SAME
-// hand-off in the HIP memory model's textbook form — plain stores, an agent-scope release fence before the ticket, an agent-scope
-// acquire fence behind it, plain loads.  +3-4 us per launch; the parity suite is run against it and its results are compared bit for
-// bit with the shipped form's.
-#ifdef NVH_HANDOFF_FENCES
-#define NVH_HANDOFF_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent")
-#define NVH_HANDOFF_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
-#else
-#define NVH_HANDOFF_RELEASE() do {} while (0)
-#define NVH_HANDOFF_ACQUIRE() do {} while (0)
-#endif
-
-// The record accesses: 16-byte items (buffer_store_dwordx4 / buffer_load_dwordx4 with sc1 through a raw
-// buffer descriptor of the (sequence, kv head)'s record group: the compiler sees them as memory operations and counts their vmcnt,
-// which inline-asm global_* accesses would leave to hand-placed waits).  Byte offsets; out-of-range accesses cannot happen (the
-// descriptor spans exactly the group).
-#ifdef NVH_HANDOFF_FENCES
-constexpr int kRecAux = 0;
-#else
-constexpr int kRecAux = 16;                               // gfx940+ cache-policy bits of the buffer intrinsics: 1 = sc0, 2 = nt, 16 = sc1
-#endif
-typedef __amdgpu_buffer_rsrc_t RecBuf;
-__device__ __forceinline__ RecBuf rec_buffer(float* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);     // raw buffer, 32-bit data format word of gfx9
-}
-__device__ __forceinline__ void st16_sc1(RecBuf rb, uint32_t byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rb, (int)byte_off, 0, kRecAux);
-}
-__device__ __forceinline__ f32x4 ld16_sc1(RecBuf rb, uint32_t byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (int)byte_off, 0, kRecAux));
-}
-// the same for any wave-uniform range, always L1-bypassing (the fused launch's hand-off reads q and the newest K / V row this way)
-typedef __amdgpu_buffer_rsrc_t RawBuf;
-__device__ __forceinline__ RawBuf raw_buffer(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ u32x4 ld16_raw_sc1(RawBuf rb, uint32_t byte_off) {
+// a 16-byte load through a descriptor of any wave-uniform range (handoff.h rec_buffer), ALWAYS L1-bypassing whatever the chunk
+// hand-off's flavour: the fused launch's producer -> consumer hand-off reads q and the newest K / V row this way
+__device__ __forceinline__ u32x4 ld16_raw_sc1(RecBuf rb, uint32_t byte_off) {
     return __builtin_amdgcn_raw_buffer_load_b128(rb, (int)byte_off, 0, 16);
 }
 
@@ -151,8 +84,8 @@ __device__ __forceinline__ u32x4 ld16_raw_sc1(RawBuf rb, uint32_t byte_off) {
 //   * each wave owns two K + V image pairs (double buffer) and runs the online softmax over its passes without any
 //     workgroup barrier: pass p+1's LDS-DMA is issued before pass p is consumed, behind counted vmcnt waits.
 //   * the waves merge through LDS once; with more than one live chunk the workgroup publishes its (max, sum, O) record
-//     write-through (16-byte sc1 stores, vmcnt(0), barrier, ticket by a relaxed agent atomic) and the LAST ARRIVER of the
-//     (sequence, kv head) merges all records (16-byte sc1 loads) and writes the output: no combine launch (-4.7 us per layer),
+//     and the LAST ARRIVER of the (sequence, kv head) merges all records and writes the output (the fence-free hand-off
+//     of handoff.h, 16-byte record items): no combine launch (-4.7 us per layer),
 //     deterministic merge order.  The release/acquire-fence form of this hand-off cost more than the launch it saved
 //     (profiles/r01_gemm_phase_stamps.txt has the same measurement for the split-K GEMM).
 // What a FUSED consumer waits on (qkv_attend.hip).  The producers of kv head kh's group (the workgroups that compute the q heads of the
@@ -452,7 +385,7 @@ __device__ __forceinline__ void decode_chunked_body(
         // the q image of the workgroup, filled by wave 0 behind its poll: row R = head min(R, G - 1), chunk order swizzled as the LDS-DMA of
         // the stand-alone kernel leaves it (the operand reads below are the same)
         fused_ok = fused_wait(fs, kh, tid, lds_ticket, fused_drawn, [&] {
-            const RawBuf qb = raw_buffer(a.q + (int64_t)b * a.q_row_stride + (int64_t)(kh * G) * D, (uint32_t)(G * D * 2));
+            const RecBuf qb = rec_buffer(a.q + (int64_t)b * a.q_row_stride + (int64_t)(kh * G) * D, (uint32_t)(G * D * 2));
             u32x4 qv[QI];
 #pragma unroll
             for (int i = 0; i < QI; ++i) {
@@ -469,7 +402,7 @@ __device__ __forceinline__ void decode_chunked_body(
             for (int st = 0; st < STEPS; ++st)
                 qf[st] = *reinterpret_cast<const bf16x8*>(lds_q + lq * ROWB + (((4 * st + lg) ^ chunk_swizzle<LPT>(lq)) * 16));
             if (holds_new) {
-                const RawBuf kb = raw_buffer(p_k_cache + new_row_off, (uint32_t)ROWB), vb = raw_buffer(p_v_cache + new_row_off, (uint32_t)ROWB);
+                const RecBuf kb = rec_buffer(p_k_cache + new_row_off, (uint32_t)ROWB), vb = rec_buffer(p_v_cache + new_row_off, (uint32_t)ROWB);
 #pragma unroll
                 for (int i = 0; i < PN; ++i) {
                     const int idx = i * 64 + lane, T = (idx / LPT) & (WT - 1), pch = idx % LPT;
@@ -739,80 +672,30 @@ __device__ __forceinline__ void decode_chunked_body(
             const int it = tid + e * WAVES * 64;
             if (it < n_items) {
                 const int g = (4 * it) >> DSH;
-                st16_sc1(rb, mine + 16 * (it + g), Ov[e]);                        // row g starts at float g * (D + 4)
-                if (((4 * it) & (D - 1)) == 0) st16_sc1(rb, mine + 4 * (g * (D + 4) + D), f32x4{Mv[e], Lv[e], 0.f, 0.f});
+                st16(rb, mine + 16 * (it + g), Ov[e]);                            // row g starts at float g * (D + 4)
+                if (((4 * it) & (D - 1)) == 0) st16(rb, mine + 4 * (g * (D + 4) + D), f32x4{Mv[e], Lv[e], 0.f, 0.f});
             }
         }
         NVH_TSTAMP(2);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        NVH_TSTAMP(3);
-        if (tid == 0) {
-            NVH_HANDOFF_RELEASE();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            // one ticket per 128-byte line: the memory side executes the adds on one line one after the other (~12 ns each); with
-            // dense tickets the 16-32 pairs that share a line made every pair's last arriver queue behind all their adds
-            unsigned* const ctr = e_counters + t_ctr_off;
-            const unsigned old = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *lds_ticket = old;
-            NVH_HANDOFF_ACQUIRE();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
+        const bool last = handoff_arrive(lds_ticket, [&] { return e_counters + t_ctr_off; }, live_chunks);
         NVH_TSTAMP(4);
-        if (*lds_ticket != (unsigned)live_chunks - 1) {        // workgroup-uniform
+        if (!last) {                                           // workgroup-uniform
             if constexpr (FUSED) fused_release(fs, kh, tid, fused_drawn);
             return;
         }
-        // the last arriver zeroes the ticket for the next launch.  Issued here, behind the barrier, and not next to the add: the
-        // barrier's wait would hold the whole workgroup until this store is acknowledged (~0.2 us on the launch's critical path);
-        // now it completes under the record loads (the kernel's end waits for it like for the output stores)
-        if (tid == 0)
-            __hip_atomic_store(e_counters + t_ctr_off, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // records are requested CB at a time (every load of a batch in flight together); four chunks, the common shape of a
         // full launch, are one batch of 8 loads per thread rather than an 8-wide batch with half of it repeated
         auto merge_chunks = [&](auto cb_tag) {
-            constexpr int CB = decltype(cb_tag)::value;
 #pragma unroll
             for (int e = 0; e < IPT; ++e) {
                 const int it = tid + e * WAVES * 64;
                 if (it < n_items) {
                     const int g = (4 * it) >> DSH;
-                    float M = -INFINITY, L = 0.f;
-                    f32x4 ov = f32x4{0.f, 0.f, 0.f, 0.f};
-                    for (int c0 = 0; c0 < live_chunks; c0 += CB) {
-                        f32x4 ml[CB], av[CB];
-#pragma unroll
-                        for (int i = 0; i < CB; ++i) {
-                            const int c = c0 + i < live_chunks ? c0 + i : live_chunks - 1;
-                            const uint32_t r = (uint32_t)(c * rec * 4);
-                            ml[i] = ld16_sc1(rb, r + 4 * (g * (D + 4) + D));
-                            av[i] = ld16_sc1(rb, r + 16 * (it + g));
-                        }
-                        // every load of the batch is ISSUED here, before any is consumed: left alone, hipcc sank the last load of an 8-wide batch
-                        // into the `c0 + i < live_chunks` block that uses it — behind the wait for the other fifteen, a second memory-side round
-                        // trip (0.6 us) in the last arriver of every pair split over 5-8 workgroups (stamped: 1.24 us for this step at 7/1/128)
-#pragma unroll
-                        for (int i = 0; i < CB; ++i) asm volatile("" : "+v"(ml[i]), "+v"(av[i]));
-                        float Mc = M;
-#pragma unroll
-                        for (int i = 0; i < CB; ++i)
-                            if (c0 + i < live_chunks) Mc = fmaxf(Mc, ml[i][0]);
-                        const float fo = fast_exp2(M - Mc);        // M = -inf on the first group -> 0
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) ov[j] *= fo;
-                        L *= fo;
-#pragma unroll
-                        for (int i = 0; i < CB; ++i)
-                            if (c0 + i < live_chunks) {
-                                const float f = fast_exp2(ml[i][0] - Mc);
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) ov[j] = fmaf(av[i][j], f, ov[j]);
-                                L = fmaf(ml[i][1], f, L);
-                            }
-                        M = Mc;
-                    }
-                    Lv[e] = L; Ov[e] = ov;
+                    f32x4 ov[1];
+                    handoff_merge<decltype(cb_tag)::value, 1, false>(
+                        rb, live_chunks, [&](int c) { return (uint32_t)(c * rec * 4) + 4 * (g * (D + 4) + D); },
+                        [&](int c, int) { return (uint32_t)(c * rec * 4) + 16 * (it + g); }, ov, Lv[e]);
+                    Ov[e] = ov[0];
                 }
             }
         };

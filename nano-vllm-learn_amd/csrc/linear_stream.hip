@@ -28,22 +28,18 @@
 //     launch's load phase.  Launches are therefore shaped to at most 256 EQUAL workgroups where the shape allows: down_proj
 //     takes 5 pieces per wave (PM) so that 56 tiles x 4 splits = 224 (not 280), gate_up uses WIDE tiles of 24 + 24
 //     columns -> 203 workgroups (not 304).  (Fewer, fatter workgroups than that lose: see DESIGN.md section 8.)
-// Hand-off (split-K), fence-free form: the partials are stored write-through (relaxed agent-scope atomic stores = `sc1`
-// stores), every storing wave drains them (s_waitcnt vmcnt(0)), workgroup barrier, lane 0 takes the ticket (relaxed agent
-// atomic add); the workgroup whose add came last reads all partials with `sc1` loads (relaxed agent-scope atomic loads) after
-// a workgroup barrier the ticket holder joins.  A release/acquire fence pair here cost 4-5 us per launch (whole-L2
-// write-back + invalidate under 280 workgroups; profiles/r01_gemm_phase_stamps.txt).
+// Hand-off (split-K): the fence-free protocol of handoff.h with 4-byte record items (st_sc1 / ld_sc1), one ticket per tile.  A
+// release/acquire fence pair here cost 4-5 us per launch (whole-L2 write-back + invalidate under 280 workgroups;
+// profiles/r01_gemm_phase_stamps.txt).
 #include <cstdlib>
 #include "common.h"
+#include "handoff.h"
 #include "kernels.h"
 
 namespace nvh {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kTicketWords = NVH_TICKET_WORDS;    // uint32 words between two tiles' arrival tickets: one ticket per 128-byte line
 constexpr int SW = 4;                          // waves per workgroup
 constexpr unsigned kMultiWgs = 512;            // workgroups of a MULTI launch (the LM head): two per CU, a power of two
 constexpr int PMAX = 4;                        // pieces (2 k-steps = 64 K-elements = one 128-byte line per weight row) per wave
@@ -57,14 +53,6 @@ constexpr int PMAX = 4;                        // pieces (2 k-steps = 64 K-eleme
 #else
 #define LS_STAMP(k) do {} while (0)
 #endif
-
-// write-through store / cache-bypassing load of one float (compile to global_store_dword / global_load_dword with sc1)
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-    __hip_atomic_store(reinterpret_cast<unsigned*>(p), __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_sc1(const float* p) {
-    return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
 
 // workgroup barrier behind this wave's LDS traffic only.  __syncthreads() also waits vmcnt(0): inside the multi-tile loop that is the NEXT
 // tile's weight DMA, issued at the top of the iteration precisely so that it travels under this tile's reduction and epilogue
@@ -496,17 +484,7 @@ __global__ __launch_bounds__(NWV * 64) void linear_stream_kernel(
                     st_sc1(part + NB * MT * 256 + tid, t);
                 }
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                const unsigned old = __hip_atomic_fetch_add(&e_counters[tile * kTicketWords], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *lds_ticket = old;
-            }
-            __syncthreads();
-            if (*lds_ticket != (unsigned)p_ksplit - 1) return;       // workgroup-uniform; MULTI never splits K
-            // zero the ticket for the next launch: behind the barrier (whose wait would otherwise hold the workgroup until the store
-            // is acknowledged), so that it completes under the partial loads
-            if (tid == 0) __hip_atomic_store(&e_counters[tile * kTicketWords], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!handoff_arrive(lds_ticket, [&] { return &e_counters[tile * kTicketStride]; }, p_ksplit)) return;   // workgroup-uniform; MULTI never splits K
             const float* const base = e_ws + (int64_t)tile * p_ksplit * PSTRIDE;
             // partials are requested SB splits at a time, all loads of a batch in flight together; up to four splits (the
             // balanced down_proj shape) are one batch instead of an 8-wide one with half of it repeated
@@ -750,7 +728,7 @@ size_t linear_stream_workspace_bytes(int m, int n, int k, int epi) {
     if (ksplit <= 1) return 0;
     const int nb = (epi == EPI_SILU || epi == EPI_ROPE) ? 2 : 1, mt = (m + 15) / 16;
     const int tiles = nb == 2 ? n / 32 : n / 16;
-    return (size_t)tiles * kTicketWords * 4 + (size_t)tiles * ksplit * (nb * mt * 256 + mt * 16) * 4;
+    return (size_t)tiles * kTicketStride * 4 + (size_t)tiles * ksplit * (nb * mt * 256 + mt * 16) * 4;
 }
 
 // Returns -100 when the call is not this kernel's (the caller falls back to skinny_gemm.hip's loop kernel).
@@ -764,7 +742,7 @@ int launch_linear_stream(const LinearArgs& a_in, hipStream_t stream) {
     const int pieces = a.K / 64;
     a.ksplit = (pieces + SW * PMAX - 1) / (SW * PMAX);
     if (a.ksplit > 1) {
-        const size_t counters_bytes = (size_t)a.tiles * kTicketWords * 4;
+        const size_t counters_bytes = (size_t)a.tiles * kTicketStride * 4;
         const int nb = (a.epi == EPI_SILU || a.epi == EPI_ROPE) ? 2 : 1, mt = (a.M + 15) / 16;
         if (!a.ws_raw || a.ws_bytes < counters_bytes + (size_t)a.tiles * a.ksplit * (nb * mt * 256 + mt * 16) * 4) return -100;
         a.counters = reinterpret_cast<unsigned*>(a.ws_raw);

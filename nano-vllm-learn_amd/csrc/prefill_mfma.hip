@@ -40,9 +40,6 @@ namespace nvh {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 // Diagnostic build only (-DNVH_STAMPS, tools/probes/stamp_prefill.py): wave 0 of every workgroup records the clock at
 // fixed points (slot k of 32 per workgroup).  Never compiled into the shipped library.
 #ifdef NVH_STAMPS
@@ -75,40 +72,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 // loop, heaviest-first grid): D=128 +18.5 % (482 -> 571 TFLOP/s at S=4096), D=64 +6.6 % at S=4096, neutral at S=1024.
 constexpr int BN = 64;      // keys per LDS tile
 
-// ds_read_b64_tr_b16 through inline asm: the builtin form makes hipcc wait vmcnt(0) before the read (it cannot prove the read
-// does not alias the LDS-DMA of the NEXT tile that is still in flight), which serialised the double buffer.  The caller
-// issues a batch of these, then `s_waitcnt lgkmcnt(0)` + a scheduling fence before the first use (guide rule 18).
-template <int OFF>
-__device__ __forceinline__ u32x2 ds_read_tr16_b64_asm(uint32_t lds_addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
-    u32x2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
-    return r;
-}
-__device__ __forceinline__ uint32_t lds_offset(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-// one v_max3_f32: plain fmaxf on MFMA outputs makes hipcc emit a canonicalising v_max x,x before every use
-__device__ __forceinline__ float max3(float x, float y, float z) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
-    return r;
-}
-
-template <int LPT>
-__device__ __forceinline__ int chunk_swz(int row) {
-    return LPT == 8 ? ((row >> 1) & 7) : (row & 15);
-}
-
-// The V image has its own swizzle: its transposed reads (ds_read_b64_tr_b16) bank per 32-lane half, where lanes address rows
-// r and r+2 (128-byte rows) / r and r+1 (256-byte rows) on the same banks; with the K swizzle those pairs land on the same
-// chunk pair (2-way conflict on every V read: a third of all LDS cycles, SQ_LDS_BANK_CONFLICT).  Even XOR values that differ
-// for the 4 (8) rows of a bank class make the 32 lanes hit 32 distinct 8-byte slots.  Rows r, r+16, r+32 share a value.
-template <int LPT>
-__device__ __forceinline__ int chunk_swz_v(int row) {
-    return LPT == 8 ? (row & 6) : ((2 * row) & 14);
-}
-
 // one v_cvt_pk_bf16_f32 (round to nearest even): {lo half = a, hi half = b}.  A vector conversion, not inline asm: hipcc pads every
 // asm statement whose result the next VALU instruction reads with an s_nop, 40 of them per tile here
 __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
@@ -126,7 +89,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
 // F16V (measurement variant, NVH_PREFILL_TILED_F16V of nvh_prefill_varlen_variant): `v` holds fp16 rows (the caller converted them; same layout
 // and strides), P is rounded to fp16 and P V is ONE v_mfma_f32_16x16x32_f16 per operand pair — no lo half.  Everything else is the same code.
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // grid (H, B, q-tiles) -> this workgroup's (q-tile, head, sequence).  Workgroups are dispatched x-fastest, so the q-tile index is the SLOW dimension
 // and runs backwards: under the causal mask tile t costs t+1 key tiles, and dispatching the heaviest tiles of every (sequence, head) first leaves
 // the light ones for the tail (census in tools/probes/stamp_prefill.py: the old x = q-tile order spent the last 40 % of the launch draining a
@@ -225,8 +187,8 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
 #pragma unroll
     for (int j = 0; j < NIW; ++j) {
         const int R = (wave * NIW + j) * TPI + dr;
-        koff[j] = (uint32_t)(R * kstride + (dp ^ chunk_swz<LPT>(R)) * 8);
-        voff[j] = (uint32_t)(R * vstride + (dp ^ chunk_swz_v<LPT>(R)) * 8);
+        koff[j] = (uint32_t)(R * kstride + (dp ^ chunk_swizzle<LPT>(R)) * 8);
+        voff[j] = (uint32_t)(R * vstride + (dp ^ chunk_swizzle_v<LPT>(R)) * 8);
     }
     auto stage = [&](int tile, int buf, const bool do_k = true, const bool do_v = true) {
         unsigned char* kimg = lds + buf * 2 * IMG;
@@ -251,8 +213,8 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
             if (ragged) {
                 const int R = ins * TPI + dr;
                 const int Rc = kv0 + R < sk ? R : sk - 1 - kv0;
-                ko = (uint32_t)(Rc * kstride + (dp ^ chunk_swz<LPT>(R)) * 8);
-                vo = (uint32_t)(Rc * vstride + (dp ^ chunk_swz_v<LPT>(R)) * 8);
+                ko = (uint32_t)(Rc * kstride + (dp ^ chunk_swizzle<LPT>(R)) * 8);
+                vo = (uint32_t)(Rc * vstride + (dp ^ chunk_swizzle_v<LPT>(R)) * 8);
             }
             if (do_k) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + ko),
                                                        (__attribute__((address_space(3))) void*)(kimg + ins * 1024), 16, 0, 0);
@@ -310,8 +272,8 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
     const int vq = lq >> 2, vp = lq & 3;
     uint32_t vaddr[DT];
     {
-        const int R0 = 4 * lg + vq;                  // chunk_swz_v(R0) == chunk_swz_v(R0 + 16) == chunk_swz_v(R0 + 32)
-        const int swz = chunk_swz_v<LPT>(R0);
+        const int R0 = 4 * lg + vq;                  // chunk_swizzle_v(R0) == chunk_swizzle_v(R0 + 16) == chunk_swizzle_v(R0 + 32)
+        const int swz = chunk_swizzle_v<LPT>(R0);
 #pragma unroll
         for (int t = 0; t < DT; ++t) vaddr[t] = lds_offset(lds + R0 * ROWB + (vp & 1) * 8 + (((2 * t + (vp >> 1)) ^ swz) * 16));
     }
@@ -341,7 +303,7 @@ __device__ __forceinline__ bool prefill_varlen_body(const PrefillArgs& a, unsign
                 const int R = 16 * tt + lq;
 #pragma unroll
                 for (int st = 0; st < STEPS; ++st) {
-                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kimg + R * ROWB + (((4 * st + lg) ^ chunk_swz<LPT>(R)) * 16));
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kimg + R * ROWB + (((4 * st + lg) ^ chunk_swizzle<LPT>(R)) * 16));
 #pragma unroll
                     for (int qs = 0; qs < QT; ++qs) sT[qs][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qs][st], sT[qs][tt], 0, 0, 0);
                 }
@@ -621,8 +583,8 @@ void prefill_short_kernel(const PrefillArgs a) {
             const int R = j * TPI + dr;                                          // row inside the tile
             const int key = tile * BN + R;
             const int kc = key < sk ? key : sk - 1;                              // rows past the end repeat the last key (masked)
-            const uint16_t* kp = a.k + (int64_t)(k_beg + kc) * a.k_row_stride + (int64_t)kh * D + (dp ^ chunk_swz<LPT>(R)) * 8;
-            const uint16_t* vp = a.v + (int64_t)(k_beg + kc) * a.v_row_stride + (int64_t)kh * D + (dp ^ chunk_swz_v<LPT>(R)) * 8;
+            const uint16_t* kp = a.k + (int64_t)(k_beg + kc) * a.k_row_stride + (int64_t)kh * D + (dp ^ chunk_swizzle<LPT>(R)) * 8;
+            const uint16_t* vp = a.v + (int64_t)(k_beg + kc) * a.v_row_stride + (int64_t)kh * D + (dp ^ chunk_swizzle_v<LPT>(R)) * 8;
             unsigned char* const kimg = lds + tile * 2 * IMG + j * 1024;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)kp, (__attribute__((address_space(3))) void*)kimg, 16, 0, 0);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)vp, (__attribute__((address_space(3))) void*)(kimg + IMG), 16, 0, 0);
@@ -687,7 +649,7 @@ void prefill_short_kernel(const PrefillArgs a) {
     uint32_t vaddr[DT];
     {
         const int R0 = 4 * lg + vq;
-        const int swz = chunk_swz_v<LPT>(R0);
+        const int swz = chunk_swizzle_v<LPT>(R0);
 #pragma unroll
         for (int tt = 0; tt < DT; ++tt) vaddr[tt] = lds_offset(lds + R0 * ROWB + (vp & 1) * 8 + (((2 * tt + (vp >> 1)) ^ swz) * 16));
     }
@@ -730,7 +692,7 @@ void prefill_short_kernel(const PrefillArgs a) {
                     const int R = 16 * tt + lq;
 #pragma unroll
                     for (int st = 0; st < STEPS; ++st) {
-                        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kimg + R * ROWB + (((4 * st + lg) ^ chunk_swz<LPT>(R)) * 16));
+                        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kimg + R * ROWB + (((4 * st + lg) ^ chunk_swizzle<LPT>(R)) * 16));
                         sT[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[st], sT[tt], 0, 0, 0);
                     }
                 } else {

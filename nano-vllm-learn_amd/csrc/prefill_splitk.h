@@ -2,22 +2,18 @@
 // The tiled body runs unchanged on each split's contiguous tile range; what differs is the end: with more than one live split a workgroup does not
 // normalise and write `out` but publishes its partial — un-normalised O^T (fp32), running max (log2 domain) and row sum per query row — as a record,
 // takes the q-tile's ticket, and the LAST ARRIVER merges all live records in split order, so the result does not depend on who arrives last.
-// The protocol is the decode kernel's (decode_chunked.h): 16-byte write-through (sc1) stores through a raw buffer descriptor of the
-// q-tile's record group, s_waitcnt vmcnt(0) in every wave, workgroup barrier, ONE relaxed agent-scope add on the q-tile's own ticket line, LDS broadcast +
-// barrier, then 16-byte L1-bypassing (sc1) loads.  No fence, no spin-wait; the last arriver stores the ticket back to zero behind the barrier.
+// The protocol and the merge are handoff.h's; this file lays out the record.
 // Record: 64 rows of [D floats of O | max | sum | 0 | 0] = 64 * (D + 4) * 4 bytes, a multiple of 256 (no line shared between two workgroups' records).
 // A thread writes exactly the elements its MFMA accumulators hold (row = its query column, 4 contiguous dims per 16-dim tile) and the merging
 // workgroup's thread reads the same elements back: no transpose, no LDS.
 #pragma once
 #include "common.h"
+#include "handoff.h"
 #include "kernels.h"
 
 namespace nvh {
 
 namespace {
-
-constexpr int kSkRecAux = 16;                // gfx940+ cache-policy bits of the buffer intrinsics: 16 = sc1
-typedef __amdgpu_buffer_rsrc_t SkRecBuf;
 
 // which key tiles split `split` of `key_splits` walks when the q-tile sees `n_tiles`: live = min(key_splits, n_tiles) splits share them in contiguous,
 // balanced ranges (sizes differ by at most one).  Every workgroup of the q-tile computes the same partition; splits at or past `live` have nothing to do.
@@ -39,68 +35,15 @@ __device__ __forceinline__ bool splitk_handoff(const PrefillArgs& a, unsigned ch
     constexpr uint32_t ROWB = (D + 4) * 4, REC = 64 * ROWB;
     constexpr int CB = D == 64 ? 4 : 2;      // records requested together: CB * (DT + 1) 16-byte loads in flight per thread
     static_assert(REC == splitk_record_bytes(D), "the plan's record size");
-    float* const recs = a.sk_records + (int64_t)unit * a.key_splits * (REC / 4);
-    const SkRecBuf rb = __builtin_amdgcn_make_buffer_rsrc(recs, 0, (int)(live * REC), 0x00020000);   // spans exactly the live records of this q-tile
-    const uint32_t mine = (uint32_t)split * REC + (uint32_t)row * ROWB, dcol = 16 * lg;
+    const RecBuf rb = rec_buffer(a.sk_records + (int64_t)unit * a.key_splits * (REC / 4), (uint32_t)(live * REC));   // spans exactly the live records of this q-tile
+    const uint32_t rowoff = (uint32_t)row * ROWB, mine = (uint32_t)split * REC + rowoff, dcol = 16 * lg;
 #pragma unroll
-    for (int t = 0; t < DT; ++t) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[t]), rb, (int)(mine + 64 * t + dcol), 0, kSkRecAux);
-    if (lg == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{m, l, 0.f, 0.f}), rb, (int)(mine + 4 * D), 0, kSkRecAux);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's share of the record has reached the memory side
-    __syncthreads();                                             // ... and every wave's
-    unsigned* const lds_ticket = reinterpret_cast<unsigned*>(lds);
-    unsigned* const ctr = a.sk_tickets + (int64_t)unit * kTicketStride;
-    if (threadIdx.x == 0) {
-        *lds_ticket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    if (*lds_ticket != (unsigned)live - 1) return false;         // workgroup-uniform
-    if (threadIdx.x == 0) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next launch; completes under the record loads
-    const uint32_t rowoff = (uint32_t)row * ROWB;
-    float M = -INFINITY, L = 0.f;
-    f32x4 acc[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int c0 = 0; c0 < live; c0 += CB) {
-        f32x4 ml[CB], av[CB][DT];
-#pragma unroll
-        for (int i = 0; i < CB; ++i) {
-            const uint32_t r = (uint32_t)(c0 + i < live ? c0 + i : live - 1) * REC + rowoff;      // (a batch's surplus slots repeat the last record and are skipped below)
-            ml[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (int)(r + 4 * D), 0, kSkRecAux));
-#pragma unroll
-            for (int t = 0; t < DT; ++t) av[i][t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, (int)(r + 64 * t + dcol), 0, kSkRecAux));
-        }
-        // every load of the batch is issued before any is consumed (see the same statement in decode_chunked.h)
-#pragma unroll
-        for (int i = 0; i < CB; ++i) {
-            asm volatile("" : "+v"(ml[i]));
-#pragma unroll
-            for (int t = 0; t < DT; ++t) asm volatile("" : "+v"(av[i][t]));
-        }
-        float Mc = M;
-#pragma unroll
-        for (int i = 0; i < CB; ++i)
-            if (c0 + i < live) Mc = fmaxf(Mc, ml[i][0]);
-        const float Mu = Mc == -INFINITY ? 0.f : Mc;             // a row no split has seen a key for: keep exp2 finite (its sum stays 0)
-        const float fo = fast_exp2(M - Mu);                      // M = -inf on the first batch -> 0
-        L *= fo;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) acc[t] *= fo;
-#pragma unroll
-        for (int i = 0; i < CB; ++i)
-            if (c0 + i < live) {
-                const float f = fast_exp2(ml[i][0] - Mu);
-                L = fmaf(ml[i][1], f, L);
-#pragma unroll
-                for (int t = 0; t < DT; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[t][j] = fmaf(av[i][t][j], f, acc[t][j]);
-            }
-        M = Mc;
-    }
-    l = L;
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[t] = acc[t];
+    for (int t = 0; t < DT; ++t) st16(rb, mine + 64 * t + dcol, o[t]);
+    if (lg == 0) st16(rb, mine + 4 * D, f32x4{m, l, 0.f, 0.f});
+    if (!handoff_arrive(reinterpret_cast<unsigned*>(lds), a.sk_tickets + (int64_t)unit * kTicketStride, live)) return false;   // workgroup-uniform
+    // a row that no split has seen a key for can occur here (EMPTY_ROWS): its sum stays 0
+    handoff_merge<CB, DT, true>(rb, live, [&](int c) { return (uint32_t)c * REC + rowoff + 4 * D; },
+                                [&](int c, int t) { return (uint32_t)c * REC + rowoff + 64 * t + dcol; }, o, l);
     return true;
 }
 

@@ -29,8 +29,6 @@ namespace nvh {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // Diagnostic build only (-DNVH_STAMPS, tools/probes/stamp_gemm.py): per-wave clock stamps, 8 slots per wave, 8 waves per workgroup
 #ifdef NVH_STAMPS
 #define GM_STAMP(k)                                                                                             \

@@ -55,11 +55,11 @@ def main():
     st = stamps.cpu().numpy().reshape(-1, waves, 8).astype(np.float64) * 0.01     # us
     st = st[st[:, 0, 1] > 0]                                                   # live workgroups only
     t0 = st[:, :, 0].min()
-    names = ["start", "waves merged in LDS", "record stores issued", "stores acknowledged + barrier", "ticket returned + barrier", "records read + merged (last arriver)",
+    names = ["start", "waves merged in LDS", "record stores issued", "(unused)", "arrived: stores acknowledged, ticket returned (handoff_arrive)", "records read + merged (last arriver)",
              "all passes done", "written (last arriver)"] if args.tail else ["start", "scalars+branch", "first loads issued", "first K landed", "first QK+softmax done", "first V landed", "all passes done",
              "merged + written (last arriver)"]
     print(f"live workgroups {st.shape[0]}, kernel span {st[:, :, 7].max() - t0:.2f} us (first wave start -> last wave end)")
-    order = [0, 6, 1, 2, 3, 4, 5, 7] if args.tail else list(range(8))
+    order = [0, 6, 1, 2, 4, 5, 7] if args.tail else list(range(8))
     for pos, k in enumerate(order):
         n = names[k]
         ok = st[:, :, k] > 0
@@ -77,7 +77,7 @@ def main():
         print(f"  per workgroup: wave skew at the end of the passes med {np.median(done - first_done):.2f} max {(done - first_done).max():.2f}; "
               f"last wave done -> merged med {np.median(merged - done):.2f} max {(merged - done).max():.2f}")
         last = st[:, 0, 5] > 0
-        seq = [6, 1, 2, 3, 4, 5, 7]
+        seq = [6, 1, 2, 4, 5, 7]
         tl = [np.median(st[last][:, :, k].max(axis=1) - t0) for k in seq]
         print("  last arrivers (median abs, max over waves):", " ".join(f"{names[k].split(' (')[0]}={v:.2f}" for k, v in zip(seq, tl)))
         starts = st[:, :, 0].min(axis=1) - t0
