@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NVH_VERSION 208          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk; 208: nvh_sample_rows / nvh_sample_advance / nvh_gumbel_noise, nvh_linear_desc.sample_* */
+#define NVH_VERSION 209          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk; 208: nvh_sample_rows / nvh_sample_advance / nvh_gumbel_noise, nvh_linear_desc.sample_*; 209: nvh_sample_rows_truncated / nvh_sample_advance_truncated */
 
 /* dtype codes */
 #define NVH_BF16 0
@@ -337,6 +337,32 @@ int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row
                        int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
                        const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream);
 int nvh_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, void* stream);
+/*   Top-k / top-p (nucleus) sampling: the same Gumbel-max over a truncated column set, which samples exactly the renormalised
+ *   truncated softmax.  top_ks int32 [n_rows], top_ps float [n_rows], both required.  Per row i, with w_j = exp((x_j - max x) / T_i):
+ *     T_i <= 0 or NaN   the greedy token, as above; top_ks / top_ps are not read
+ *     value classes     bf16 logits take at most 65536 distinct values (-0 and +0 are one); truncation keeps or drops whole classes,
+ *                       so the kept set does not depend on column order or on how ties would sort
+ *     top-k             v_k = the top_ks[i]-th largest logit of the row; keep {j : x_j >= v_k}: ties at the threshold are all kept,
+ *                       as masking `logits < kth` does.  top_ks[i] <= 0 or >= n: off
+ *     top-p             after top-k, over its survivors, Z their total weight: a class v is kept iff the weight of the survivors
+ *                       with x_j > v is < top_ps[i] * Z; the largest class is always kept.  top_ps[i] >= 1 or NaN: off;
+ *                       top_ps[i] <= 0: the largest class only
+ *     token             argmax over the kept columns of fma(T_i, g_j, x_j), the noise and the ordering of nvh_sample_rows.  With both
+ *                       truncations off it is nvh_sample_rows' token bit for bit; with top_k = 1 and a unique maximum, the greedy one
+ *     NaN logit         the lowest NaN column, as nvh_sample_rows
+ *   Weights are summed as integers (round(w * 2^40), exact and order-free) and compared with top_p * Z in fp64: a token is a pure
+ *   function of (logits row, T, top_k, top_p, seed, row key, step), the same on every replay and every rank.  A weight is fp32
+ *   (about 4e-6 relative), so a class whose weight above lies within that of top_p * Z may fall on either side of the cut.
+ *   nvh_sample_rows_truncated / nvh_sample_advance_truncated  nvh_sample_rows / nvh_sample_advance with that choice of token */
+int nvh_sample_rows_truncated(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                              const float* temperatures, const uint32_t* row_keys, const int64_t* steps,
+                              const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream);
+int nvh_sample_advance_truncated(const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                                 int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
+                                 const int32_t* block_tables, int64_t bt_row_stride, int block_size,
+                                 int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
+                                 const float* temperatures, const uint32_t* row_keys,
+                                 const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream);
 
 /*
  * Engine widening: weight-streaming linear layer for decode-sized batches, out = x . W^T (+ bias), m <= 64 rows.

@@ -506,21 +506,41 @@ int nvh_greedy_advance(const void* logits, int n_rows, int n, int64_t logits_row
     return launch_argmax_rows(nullptr, logits, n_rows, n, logits_row_stride, adv, (hipStream_t)stream);
 }
 
+struct Truncation { const int32_t* top_ks; const float* top_ps; };   // both non-null: the truncated kernel (sample_truncated.hip)
+
 static int sample_rows_impl(const char* fn, int64_t* out, const void* logits, int n_rows, int n, int64_t stride, const SampleArgs& s, const AdvanceArgs& adv,
-                            int dtype, void* stream) {
+                            int dtype, void* stream, const Truncation* tr = nullptr) {
     if (dtype != NVH_BF16) { set_error("%s: dtype %d unsupported (bf16 only)", fn, dtype); return NVH_E_DTYPE; }
-    if (!logits || !s.temperatures || !s.row_keys || (!s.steps && !adv.row_steps)) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
+    if (!logits || !s.temperatures || !s.row_keys || (!s.steps && !adv.row_steps) || (tr && (!tr->top_ks || !tr->top_ps))) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
     if (n_rows < 0 || n <= 0) { set_error("%s: bad shape", fn); return NVH_E_SHAPE; }
     if (stride % 8 || stride < n) { set_error("%s: logits row stride must be a multiple of 8 and >= n", fn); return NVH_E_STRIDE; }
     if (!aligned16(logits)) { set_error("%s: logits must be 16-byte aligned", fn); return NVH_E_ALIGN; }
+    if (tr) return launch_sample_truncated(out, logits, n_rows, n, stride, s, tr->top_ks, tr->top_ps, adv, (hipStream_t)stream);
     return launch_sample_rows(out, logits, n_rows, n, stride, s, adv, (hipStream_t)stream);
+}
+
+static int sample_rows_entry(const char* fn, int64_t* out, const void* logits, int n_rows, int n, int64_t stride, const float* temperatures,
+                             const uint32_t* row_keys, const int64_t* steps, uint64_t seed, int dtype, void* stream, const Truncation* tr) {
+    if (n_rows == 0) return 0;
+    if (!out || !steps) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
+    return sample_rows_impl(fn, out, logits, n_rows, n, stride, SampleArgs{temperatures, row_keys, steps, seed}, AdvanceArgs{}, dtype, stream, tr);
+}
+
+static int sample_advance_entry(const char* fn, const void* logits, int n_rows, int n, int64_t stride,
+                                int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
+                                const int32_t* block_tables, int64_t bt_row_stride, int block_size,
+                                int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
+                                const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream, const Truncation* tr) {
+    if (n_rows == 0) return 0;
+    if (!input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
+    if (block_size <= 0 || log_row_stride < n_rows) { set_error("%s: bad shape", fn); return NVH_E_SHAPE; }
+    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
+    return sample_rows_impl(fn, nullptr, logits, n_rows, n, stride, SampleArgs{temperatures, row_keys, nullptr, seed}, adv, dtype, stream, tr);
 }
 
 int nvh_sample_rows(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
                     const float* temperatures, const uint32_t* row_keys, const int64_t* steps, uint64_t seed, int dtype, void* stream) {
-    if (n_rows == 0) return 0;
-    if (!out || !steps) { set_error("sample_rows: null pointer"); return NVH_E_NULL; }
-    return sample_rows_impl("sample_rows", out, logits, n_rows, n, logits_row_stride, SampleArgs{temperatures, row_keys, steps, seed}, AdvanceArgs{}, dtype, stream);
+    return sample_rows_entry("sample_rows", out, logits, n_rows, n, logits_row_stride, temperatures, row_keys, steps, seed, dtype, stream, nullptr);
 }
 
 int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row_stride,
@@ -528,11 +548,26 @@ int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row
                        const int32_t* block_tables, int64_t bt_row_stride, int block_size,
                        int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
                        const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream) {
-    if (n_rows == 0) return 0;
-    if (!input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps) { set_error("sample_advance: null pointer"); return NVH_E_NULL; }
-    if (block_size <= 0 || log_row_stride < n_rows) { set_error("sample_advance: bad shape"); return NVH_E_SHAPE; }
-    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
-    return sample_rows_impl("sample_advance", nullptr, logits, n_rows, n, logits_row_stride, SampleArgs{temperatures, row_keys, nullptr, seed}, adv, dtype, stream);
+    return sample_advance_entry("sample_advance", logits, n_rows, n, logits_row_stride, input_ids, positions, context_lens, slot_mapping, block_tables,
+                                bt_row_stride, block_size, tokens_log, log_row_stride, row_steps, temperatures, row_keys, seed, dtype, stream, nullptr);
+}
+
+int nvh_sample_rows_truncated(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                              const float* temperatures, const uint32_t* row_keys, const int64_t* steps,
+                              const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream) {
+    const Truncation tr{top_ks, top_ps};
+    return sample_rows_entry("sample_rows_truncated", out, logits, n_rows, n, logits_row_stride, temperatures, row_keys, steps, seed, dtype, stream, &tr);
+}
+
+int nvh_sample_advance_truncated(const void* logits, int n_rows, int n, int64_t logits_row_stride,
+                                 int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
+                                 const int32_t* block_tables, int64_t bt_row_stride, int block_size,
+                                 int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
+                                 const float* temperatures, const uint32_t* row_keys,
+                                 const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream) {
+    const Truncation tr{top_ks, top_ps};
+    return sample_advance_entry("sample_advance_truncated", logits, n_rows, n, logits_row_stride, input_ids, positions, context_lens, slot_mapping,
+                                block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps, temperatures, row_keys, seed, dtype, stream, &tr);
 }
 
 int nvh_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, void* stream) {

@@ -119,6 +119,9 @@ int launch_argmax_rows(int64_t* out, const void* x, int n_rows, int n, int64_t s
 // sample.hip: temperature sampling of materialised logits (s.steps null: the counter is adv.row_steps) and the bare noise
 int launch_sample_rows(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const SampleArgs& s, const AdvanceArgs& adv, hipStream_t stream);
 int launch_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, hipStream_t stream);
+// sample_truncated.hip: the same over the top-k / top-p value classes of each row (top_ks int32 [rows], top_ps float [rows])
+int launch_sample_truncated(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const SampleArgs& s, const int32_t* top_ks,
+                            const float* top_ps, const AdvanceArgs& adv, hipStream_t stream);
 int launch_argmax_candidates(const float* cand_val, const int32_t* cand_idx, int groups, int64_t cand_stride, int n_rows, int vocab,
                              const AdvanceArgs& adv, hipStream_t stream);   // vocab: chosen indices are clamped to [0, vocab)
 int linear_stream_candidate_groups(int n, int k);   // workgroups (= candidate records per row) of a NONE launch, 0 if unsupported

@@ -98,6 +98,11 @@ _SIGS = {
     "nvh_sample_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
                            [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                             ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_sample_rows_truncated": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
+                                  [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
+    "nvh_sample_advance_truncated": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
+                                     [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
+                                     [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
     "nvh_gumbel_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]),
     "nvh_linear_small_m_ex": (ctypes.c_int, [ctypes.POINTER(LinearDesc), ctypes.c_int, ctypes.c_void_p]),
     "nvh_linear_small_m_workspace": (ctypes.c_size_t, [ctypes.c_int] * 4),

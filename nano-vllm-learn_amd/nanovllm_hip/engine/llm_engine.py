@@ -41,12 +41,14 @@ class LLMEngine:
             for s, t in zip(batch, self.runner.run(batch, True)):
                 s.append_token(t)
 
-    def generate(self, prompt_token_ids, max_tokens, temperature=0.0):
+    def generate(self, prompt_token_ids, max_tokens, temperature=0.0, top_k=0, top_p=1.0):
         """Generate `max_tokens` tokens for every prompt; returns the completion token ids.  temperature: one value or one per
-        prompt; 0 = greedy, > 0 = sampled as the reference's sampler.py does (noise seed: ModelConfig.seed)."""
-        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * len(prompt_token_ids)
-        assert len(temps) == len(prompt_token_ids) and all(t >= 0 for t in temps)
-        seqs = [Sequence(p, max_tokens=max_tokens, temperature=t) for p, t in zip(prompt_token_ids, temps)]
+        prompt; 0 = greedy, > 0 = sampled as the reference's sampler.py does (noise seed: ModelConfig.seed).  top_k (<= 0: off) and
+        top_p (>= 1: off), one value or one per prompt: sampled rows draw from the top-k / top-p value classes only."""
+        per_prompt = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(prompt_token_ids)
+        temps, top_ks, top_ps = per_prompt(temperature), per_prompt(top_k), per_prompt(top_p)
+        assert len(temps) == len(top_ks) == len(top_ps) == len(prompt_token_ids) and all(t >= 0 for t in temps)
+        seqs = [Sequence(p, max_tokens=max_tokens, temperature=t, top_k=k, top_p=pp) for p, t, k, pp in zip(prompt_token_ids, temps, top_ks, top_ps)]
         self.prefill(seqs, reserve_tokens=max_tokens)
         if max_tokens > 1:
             if self.enforce_eager:

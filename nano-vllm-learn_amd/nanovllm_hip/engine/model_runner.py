@@ -38,12 +38,17 @@ def greedy_tokens(logits):
 def sampling_inputs(seqs, device, steps=None):
     """What the sampling kernels read per row, or None when every request is greedy (the launches are then the greedy ones):
     temperatures float32 [b], row keys uint32 [b] (the sequence ids: the noise of a request does not depend on the batch it
-    shares) and, with `steps`, the noise counters int64 [b]."""
+    shares) and, with `steps`, the noise counters int64 [b].  When a sampled row truncates (top_k > 0 or top_p < 1), top_k int32 [b] and
+    top_p float32 [b] follow at the end: the caller then takes the truncated launch (ops.sample_rows / sample_advance with top_k, top_p)."""
     temps = [float(s.temperature) for s in seqs]
     if not any(t > 0 for t in temps):
         return None
     out = (torch.tensor(temps, dtype=torch.float32).to(device), torch.tensor([s.seq_id & 0xFFFFFFFF for s in seqs], dtype=torch.uint32).to(device))
-    return out if steps is None else out + (torch.tensor(steps, dtype=torch.int64).to(device),)
+    if steps is not None:
+        out += (torch.tensor(steps, dtype=torch.int64).to(device),)
+    if any(t > 0 and (s.top_k > 0 or s.top_p < 1) for s, t in zip(seqs, temps)):
+        out += (torch.tensor([int(s.top_k) for s in seqs], dtype=torch.int32).to(device), torch.tensor([float(s.top_p) for s in seqs], dtype=torch.float32).to(device))
+    return out
 
 
 def build_block_tables(seqs, width=None, pad=-1):
@@ -163,7 +168,7 @@ class ModelRunner:
             hidden = hidden[last]
         logits = self.model.compute_logits(hidden)
         smp = sampling_inputs(seqs, self.device, steps=[s.num_completion_tokens - 1 for s in seqs])
-        tokens = greedy_tokens(logits) if smp is None else ops.sample_rows(logits, *smp, self.cfg.seed)
+        tokens = greedy_tokens(logits) if smp is None else ops.sample_rows(logits, *smp[:3], self.cfg.seed, *smp[3:])
         reset_context()
         out = tokens.tolist()                                                         # (the host synchronises here anyway)
         self.raise_if_device_failed()
@@ -243,15 +248,18 @@ class DecodeSession:
         self.max_new_tokens = max_new_tokens
         self.steps_done = 0
         # temperature sampling: the noise counter is row_steps itself, which the advance launch increments inside the graph
+        # with top-k / top-p on some row the step materialises its logits for nvh_sample_advance_truncated (still inside the graph)
         self.sampling = sampling_inputs(seqs, dev)
+        self.truncation = None
         if self.sampling is not None:
-            self.sampling += (self.row_steps, runner.cfg.seed)
+            self.truncation = self.sampling[2:] or None
+            self.sampling = self.sampling[:2] + (self.row_steps, runner.cfg.seed)
         cfg = runner.cfg
         h = tp_partition(cfg.num_attention_heads, cfg.num_key_value_heads, runner.world_size, runner.rank)[1]
         ops.reserve_workspace(dev, ops.decode_workspace_bytes(b, h, cfg.head_dim, self.block_tables.shape[1], bs))
         # the next step's embedding lookup rides in the arg-max launch when the model allows it: the session then owns the
         # embedded rows (row-major = the residual stream of the step, and in fragment order for layer 0's projection)
-        self.fuse_embed = bool(getattr(runner.model, "fused_embedding_ok", lambda *_: False)(b, torch.device(dev)))
+        self.fuse_embed = self.truncation is None and bool(getattr(runner.model, "fused_embedding_ok", lambda *_: False)(b, torch.device(dev)))
         if self.fuse_embed:
             hid = cfg.hidden_size
             self.hidden_in = torch.zeros(b, hid, dtype=torch.bfloat16, device=dev)
@@ -301,7 +309,8 @@ class DecodeSession:
             hidden = model(self.input_ids, self.positions, embedded=(self.hidden_in, self.hidden_in_p))
         else:
             hidden = model(self.input_ids, self.positions)
-        cand = model.greedy_candidates(hidden, sampling=self.sampling)   # LM head + arg-max candidates in one launch (fused decode path)
+        # LM head + arg-max candidates in one launch (fused decode path); a truncating session needs the whole row
+        cand = None if self.truncation is not None else model.greedy_candidates(hidden, sampling=self.sampling)
         if cand is not None:
             embed = (model.embed_tokens.weight, self.hidden_in, self.hidden_in_p) if self.fuse_embed else None
             ops.greedy_advance_candidates(cand[0], cand[1], cand[2], self.batch, self.input_ids, self.positions, self.context_lens,
@@ -313,7 +322,7 @@ class DecodeSession:
         if self.sampling is not None:
             temps, keys, _, seed = self.sampling
             ops.sample_advance(logits, self.input_ids, self.positions, self.context_lens, self.slot_mapping, self.block_tables,
-                               self.runner.block_size, self.tokens, self.row_steps, temps, keys, seed)
+                               self.runner.block_size, self.tokens, self.row_steps, temps, keys, seed, *(self.truncation or ()))
         elif logits.is_cuda and logits.dtype == torch.bfloat16 and logits.stride(0) % 8 == 0:
             # sampling + postprocess + next step's prepare_decode in ONE launch (nvh_greedy_advance)
             ops.greedy_advance(logits, self.input_ids, self.positions, self.context_lens, self.slot_mapping, self.block_tables,

@@ -6,7 +6,7 @@ class Sequence:
     block_size = 256
     counter = count()
 
-    def __init__(self, token_ids, max_tokens=64, ignore_eos=True, temperature=0.0):
+    def __init__(self, token_ids, max_tokens=64, ignore_eos=True, temperature=0.0, top_k=0, top_p=1.0):
         self.seq_id = next(Sequence.counter)
         self.token_ids = list(token_ids)
         self.last_token = self.token_ids[-1]
@@ -17,6 +17,8 @@ class Sequence:
         self.max_tokens = max_tokens
         self.ignore_eos = ignore_eos
         self.temperature = temperature
+        self.top_k = top_k                    # <= 0: off; with top_p (>= 1: off) the truncation of include/nvh_attn.h, read where temperature > 0
+        self.top_p = top_p
 
     def __len__(self):
         return self.num_tokens

@@ -591,15 +591,35 @@ def _require_sampling(m, temperatures, row_keys, steps=None):
         assert steps.is_cuda and steps.dtype == torch.int64 and steps.numel() == m and steps.is_contiguous()
 
 
-def sample_rows(logits, temperatures, row_keys, steps, seed):
+def _truncation(m, device, top_k, top_p):
+    """(top_k int32 [m], top_p float32 [m]) for the truncated entry points, a missing one filled with its "off" value; None: no truncation."""
+    if top_k is None and top_p is None:
+        return None
+    top_k = torch.zeros(m, dtype=torch.int32, device=device) if top_k is None else top_k
+    top_p = torch.ones(m, dtype=torch.float32, device=device) if top_p is None else top_p
+    assert top_k.is_cuda and top_k.dtype == torch.int32 and top_k.numel() == m and top_k.is_contiguous()
+    assert top_p.is_cuda and top_p.dtype == torch.float32 and top_p.numel() == m and top_p.is_contiguous()
+    return top_k, top_p
+
+
+def sample_rows(logits, temperatures, row_keys, steps, seed, top_k=None, top_p=None):
     """Temperature sampling per row of bf16 logits [M, N] (nvh_sample_rows): argmax_j (logits[i, j] + T_i * g) with the counter-based
     Gumbel noise g(seed, row_keys[i], steps[i], j) of csrc/sample_noise.h — the distribution of the reference's sampler.py, the greedy
-    token where T_i <= 0.  temperatures float32 [M], row_keys uint32 [M], steps int64 [M] (read as uint64).  Returns int64 [M]."""
+    token where T_i <= 0.  temperatures float32 [M], row_keys uint32 [M], steps int64 [M] (read as uint64).  Returns int64 [M].
+    top_k int32 [M] / top_p float32 [M] (either may be None = off): the arg-max runs over the top-k / top-p value classes of each row
+    only (nvh_sample_rows_truncated; semantics in include/nvh_attn.h)."""
     _require_gpu_bf16(logits=logits)
     assert logits.dim() == 2 and logits.stride(1) == 1
     m = logits.shape[0]
     _require_sampling(m, temperatures, row_keys, steps)
     out = torch.empty(m, dtype=torch.int64, device=logits.device)
+    trunc = _truncation(m, logits.device, top_k, top_p)
+    if trunc is not None:
+        rc = _lib.load().nvh_sample_rows_truncated(out.data_ptr(), logits.data_ptr(), m, logits.shape[1], logits.stride(0), temperatures.data_ptr(),
+                                                   row_keys.data_ptr(), steps.data_ptr(), trunc[0].data_ptr(), trunc[1].data_ptr(),
+                                                   int(seed) & _U64, NVH_BF16, _stream())
+        _lib.check(rc, "nvh_sample_rows_truncated")
+        return out
     rc = _lib.load().nvh_sample_rows(out.data_ptr(), logits.data_ptr(), m, logits.shape[1], logits.stride(0), temperatures.data_ptr(),
                                      row_keys.data_ptr(), steps.data_ptr(), int(seed) & _U64, NVH_BF16, _stream())
     _lib.check(rc, "nvh_sample_rows")
@@ -607,9 +627,9 @@ def sample_rows(logits, temperatures, row_keys, steps, seed):
 
 
 def sample_advance(logits, input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps,
-                   temperatures, row_keys, seed):
-    """greedy_advance with sample_rows' choice of token (nvh_sample_advance); the noise step of a row is row_steps[row] before the
-    call increments it, so a captured step draws fresh noise on every replay."""
+                   temperatures, row_keys, seed, top_k=None, top_p=None):
+    """greedy_advance with sample_rows' choice of token (nvh_sample_advance; with top_k / top_p nvh_sample_advance_truncated); the noise
+    step of a row is row_steps[row] before the call increments it, so a captured step draws fresh noise on every replay."""
     _require_gpu_bf16(logits=logits)
     _require_i32(context_lens=context_lens, slot_mapping=slot_mapping, block_tables=block_tables)
     m = logits.shape[0]
@@ -618,6 +638,15 @@ def sample_advance(logits, input_ids, positions, context_lens, slot_mapping, blo
         assert t.dtype == torch.int64 and t.is_cuda
     assert tokens_log.dim() == 2 and tokens_log.shape[1] >= m and tokens_log.stride(1) == 1
     _require_sampling(m, temperatures, row_keys)
+    trunc = _truncation(m, logits.device, top_k, top_p)
+    if trunc is not None:
+        rc = _lib.load().nvh_sample_advance_truncated(
+            logits.data_ptr(), m, logits.shape[1], logits.stride(0), input_ids.data_ptr(), positions.data_ptr(), context_lens.data_ptr(),
+            slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0), block_size, tokens_log.data_ptr(), tokens_log.stride(0),
+            row_steps.data_ptr(), temperatures.data_ptr(), row_keys.data_ptr(), trunc[0].data_ptr(), trunc[1].data_ptr(), int(seed) & _U64,
+            NVH_BF16, _stream())
+        _lib.check(rc, "nvh_sample_advance_truncated")
+        return
     rc = _lib.load().nvh_sample_advance(logits.data_ptr(), m, logits.shape[1], logits.stride(0), input_ids.data_ptr(), positions.data_ptr(),
                                         context_lens.data_ptr(), slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
                                         block_size, tokens_log.data_ptr(), tokens_log.stride(0), row_steps.data_ptr(), temperatures.data_ptr(),

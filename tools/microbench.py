@@ -7,6 +7,7 @@ cycling over `--layers` distinct KV caches so that no launch re-reads what the p
 
     python tools/microbench.py decode --batch 32 --ctx 1536 --heads 14 --kv-heads 2 --head-dim 64
     python tools/microbench.py lmhead --batch 32 --hidden 896 --vocab 151936     # LM head + advance, greedy against sampled
+    python tools/microbench.py sample --batch 64 --vocab 151936                  # sample_rows against its top-k / top-p forms
 """
 import argparse
 import json
@@ -108,9 +109,34 @@ def lmhead(args, dev):
                       "sampled_over_greedy": round(sm / gm, 4), "weight_MB": round(n * k * 2 / 1e6, 1), "greedy_GBps": round(n * k * 2 / gm / 1e3, 1)}))
 
 
+def sample(args, dev):
+    """nvh_sample_rows against nvh_sample_rows_truncated on [batch, vocab] bf16 logits (3 randn, temperature 0.7 in every row) under graph
+    replay: --layers launches per graph cycling over as many distinct logits copies, the variants alternating, three repeats each."""
+    b, n = args.batch, args.vocab
+    logits = [(3 * torch.randn(b, n, device=dev)).bfloat16() for _ in range(args.layers)]
+    temps, keys, steps = torch.full((b,), 0.7, device=dev), torch.arange(b, dtype=torch.int32, device=dev), torch.zeros(b, dtype=torch.int64, device=dev)
+    i32, f32 = (lambda v: torch.full((b,), v, dtype=torch.int32, device=dev)), (lambda v: torch.full((b,), v, dtype=torch.float32, device=dev))
+    variants = {"sample_rows": {}, "truncated_off": dict(top_k=i32(0), top_p=f32(1.0)), "top_k20": dict(top_k=i32(20), top_p=f32(1.0)),
+                "top_k20_top_p0.8": dict(top_k=i32(20), top_p=f32(0.8)), "top_p0.8": dict(top_k=i32(0), top_p=f32(0.8))}
+    graphs = {}
+    for name, kw in variants.items():
+        ops.sample_rows(logits[0], temps, keys, steps, 1, **kw)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for l in range(args.layers):
+                ops.sample_rows(logits[l], temps, keys, steps, 1, **kw)
+        graphs[name] = g
+    us = {name: [] for name in graphs}
+    for _ in range(3):
+        for name, g in graphs.items():
+            us[name].append(round(time_loop(lambda l: g.replay(), 1, args.iters, args.warmup) / args.layers, 2))
+    print(json.dumps({"mode": "sample", "batch": b, "vocab": n, "launches_per_graph": args.layers, "logits_MB": round(b * n * 2 / 1e6, 1), "us": us}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["decode", "prefill", "lmhead"])
+    ap.add_argument("mode", choices=["decode", "prefill", "lmhead", "sample"])
     ap.add_argument("--hidden", type=int, default=896, help="lmhead: K")
     ap.add_argument("--vocab", type=int, default=151936, help="lmhead: N")
     ap.add_argument("--batch", type=int, default=32)
@@ -141,6 +167,8 @@ def main():
     torch.manual_seed(0)
     if args.mode == "lmhead":
         return lmhead(args, dev)
+    if args.mode == "sample":
+        return sample(args, dev)
     if args.mode == "decode":
         q, caches, cl, bt, ctxs = make_decode(args, dev)
         b, h, kvh, d = args.batch, args.heads, args.kv_heads, args.head_dim
