@@ -482,65 +482,80 @@ int nvh_silu_mul(void* out, const void* gate_up, int n_rows, int inter, int64_t 
     return launch_silu_mul(out, gate_up, n_rows, inter, gate_up_row_stride, out_row_stride, (hipStream_t)stream);
 }
 
-int nvh_argmax_rows(int64_t* out, const void* x, int n_rows, int n, int64_t x_row_stride, int dtype, void* stream) {
+// ---- token choice: nvh_argmax_rows / nvh_greedy_advance / nvh_sample_* on logits (choose_rows), nvh_greedy_advance_candidates* on
+// candidate records.  Every entry point reports its defects in ONE order: dtype, null pointers, shape, stride, alignment.
+static int defect(const char* fn, int code) {
+    set_error("%s: %s", fn, code == NVH_E_DTYPE ? "dtype unsupported (bf16 only)" : code == NVH_E_NULL ? "null pointer" : code == NVH_E_SHAPE ? "bad shape"
+                            : code == NVH_E_STRIDE ? "row stride must be a multiple of 8 and >= the row's length" : "pointers must be 16-byte aligned");
+    return code;
+}
+
+// A bf16 logits matrix [n_rows, n].  `others`: the first defect of the call's remaining arguments (0, NVH_E_NULL or NVH_E_SHAPE),
+// reported at its place in the order.
+static int check_logits(const char* fn, const void* logits, int n_rows, int n, int64_t stride, int dtype, int others) {
+    if (dtype != NVH_BF16) return defect(fn, NVH_E_DTYPE);
+    if (!logits || others == NVH_E_NULL) return defect(fn, NVH_E_NULL);
+    if (n_rows < 0 || n <= 0 || others == NVH_E_SHAPE) return defect(fn, NVH_E_SHAPE);
+    if (stride % 8 || stride < n) return defect(fn, NVH_E_STRIDE);
+    if (!aligned16(logits)) return defect(fn, NVH_E_ALIGN);
+    return 0;
+}
+
+struct EmbedLookup { const void* weight; int vocab, hidden; void* hidden_out; int64_t hidden_row_stride; void* hidden_packed; };
+
+// The advance argument run of the ABI (and, for the candidates form, the next step's embedding lookup) -> AdvanceArgs.
+// *first_defect: 0, NVH_E_NULL, NVH_E_SHAPE or NVH_E_ALIGN; the caller reports it.
+static AdvanceArgs advance_args(int* first_defect, int n_rows, int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
+                                const int32_t* block_tables, int64_t bt_row_stride, int block_size, int64_t* tokens_log, int64_t log_row_stride,
+                                int64_t* row_steps, const EmbedLookup* e = nullptr) {
+    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
+    if (e) {
+        adv.embed = (const uint16_t*)e->weight; adv.hidden = e->hidden; adv.hidden_out = (uint16_t*)e->hidden_out;
+        adv.hidden_stride = e->hidden_row_stride; adv.hidden_packed = (uint16_t*)e->hidden_packed;
+    }
+    if (!input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps || (e && (!e->weight || !e->hidden_out)))
+        *first_defect = NVH_E_NULL;
+    else if (block_size <= 0 || log_row_stride < n_rows ||
+             (e && (e->vocab <= 0 || e->hidden <= 0 || e->hidden % 32 != 0 || e->hidden_row_stride < e->hidden || e->hidden_row_stride % 8 != 0)))
+        *first_defect = NVH_E_SHAPE;             // hidden: a multiple of 32 (fragment order); its row stride a multiple of 8 and >= hidden
+    else if (e && (!aligned16(e->weight) || !aligned16(e->hidden_out) || !aligned16(e->hidden_packed)))
+        *first_defect = NVH_E_ALIGN;
+    else
+        *first_defect = 0;
+    return adv;
+}
+
+struct Truncation { const int32_t* top_ks; const float* top_ps; };   // both non-null: the truncated kernel (sample_truncated.hip)
+
+// One row of logits -> one token: `out` (required without an advance) and / or the advance; s null: greedy; tr: top-k / top-p
+static int choose_rows(const char* fn, int64_t* out, const void* logits, int n_rows, int n, int64_t stride, const SampleArgs* s, const Truncation* tr,
+                       const AdvanceArgs& adv, int adv_defect, int dtype, void* stream) {
     if (n_rows == 0) return 0;
-    if (dtype != NVH_BF16) { set_error("argmax_rows: dtype %d unsupported (bf16 only)", dtype); return NVH_E_DTYPE; }
-    if (!out || !x) { set_error("argmax_rows: null pointer"); return NVH_E_NULL; }
-    if (n_rows < 0 || n <= 0) { set_error("argmax_rows: bad shape"); return NVH_E_SHAPE; }
-    if (x_row_stride % 8 || x_row_stride < n) { set_error("argmax_rows: row stride must be a multiple of 8 and >= n"); return NVH_E_STRIDE; }
-    if (!aligned16(x)) { set_error("argmax_rows: x must be 16-byte aligned"); return NVH_E_ALIGN; }
-    return launch_argmax_rows(out, x, n_rows, n, x_row_stride, AdvanceArgs{}, (hipStream_t)stream);
+    const bool missing = (!out && !adv.input_ids) || (s && (!s->temperatures || !s->row_keys || (!s->steps && !adv.row_steps))) ||
+                         (tr && (!tr->top_ks || !tr->top_ps));
+    if (const int rc = check_logits(fn, logits, n_rows, n, stride, dtype, missing ? NVH_E_NULL : adv_defect)) return rc;
+    if (tr) return launch_sample_truncated(out, logits, n_rows, n, stride, *s, tr->top_ks, tr->top_ps, adv, (hipStream_t)stream);
+    if (s) return launch_sample_rows(out, logits, n_rows, n, stride, *s, adv, (hipStream_t)stream);
+    return launch_argmax_rows(out, logits, n_rows, n, stride, adv, (hipStream_t)stream);
+}
+
+int nvh_argmax_rows(int64_t* out, const void* x, int n_rows, int n, int64_t x_row_stride, int dtype, void* stream) {
+    return choose_rows("argmax_rows", out, x, n_rows, n, x_row_stride, nullptr, nullptr, AdvanceArgs{}, 0, dtype, stream);
 }
 
 int nvh_greedy_advance(const void* logits, int n_rows, int n, int64_t logits_row_stride,
                        int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
                        const int32_t* block_tables, int64_t bt_row_stride, int block_size,
                        int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps, int dtype, void* stream) {
-    if (n_rows == 0) return 0;
-    if (dtype != NVH_BF16) { set_error("greedy_advance: dtype %d unsupported (bf16 only)", dtype); return NVH_E_DTYPE; }
-    if (!logits || !input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps) { set_error("greedy_advance: null pointer"); return NVH_E_NULL; }
-    if (n_rows < 0 || n <= 0 || block_size <= 0 || log_row_stride < n_rows) { set_error("greedy_advance: bad shape"); return NVH_E_SHAPE; }
-    if (logits_row_stride % 8 || logits_row_stride < n) { set_error("greedy_advance: logits row stride must be a multiple of 8 and >= n"); return NVH_E_STRIDE; }
-    if (!aligned16(logits)) { set_error("greedy_advance: logits must be 16-byte aligned"); return NVH_E_ALIGN; }
-    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
-    return launch_argmax_rows(nullptr, logits, n_rows, n, logits_row_stride, adv, (hipStream_t)stream);
-}
-
-struct Truncation { const int32_t* top_ks; const float* top_ps; };   // both non-null: the truncated kernel (sample_truncated.hip)
-
-static int sample_rows_impl(const char* fn, int64_t* out, const void* logits, int n_rows, int n, int64_t stride, const SampleArgs& s, const AdvanceArgs& adv,
-                            int dtype, void* stream, const Truncation* tr = nullptr) {
-    if (dtype != NVH_BF16) { set_error("%s: dtype %d unsupported (bf16 only)", fn, dtype); return NVH_E_DTYPE; }
-    if (!logits || !s.temperatures || !s.row_keys || (!s.steps && !adv.row_steps) || (tr && (!tr->top_ks || !tr->top_ps))) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
-    if (n_rows < 0 || n <= 0) { set_error("%s: bad shape", fn); return NVH_E_SHAPE; }
-    if (stride % 8 || stride < n) { set_error("%s: logits row stride must be a multiple of 8 and >= n", fn); return NVH_E_STRIDE; }
-    if (!aligned16(logits)) { set_error("%s: logits must be 16-byte aligned", fn); return NVH_E_ALIGN; }
-    if (tr) return launch_sample_truncated(out, logits, n_rows, n, stride, s, tr->top_ks, tr->top_ps, adv, (hipStream_t)stream);
-    return launch_sample_rows(out, logits, n_rows, n, stride, s, adv, (hipStream_t)stream);
-}
-
-static int sample_rows_entry(const char* fn, int64_t* out, const void* logits, int n_rows, int n, int64_t stride, const float* temperatures,
-                             const uint32_t* row_keys, const int64_t* steps, uint64_t seed, int dtype, void* stream, const Truncation* tr) {
-    if (n_rows == 0) return 0;
-    if (!out || !steps) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
-    return sample_rows_impl(fn, out, logits, n_rows, n, stride, SampleArgs{temperatures, row_keys, steps, seed}, AdvanceArgs{}, dtype, stream, tr);
-}
-
-static int sample_advance_entry(const char* fn, const void* logits, int n_rows, int n, int64_t stride,
-                                int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
-                                const int32_t* block_tables, int64_t bt_row_stride, int block_size,
-                                int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
-                                const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream, const Truncation* tr) {
-    if (n_rows == 0) return 0;
-    if (!input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps) { set_error("%s: null pointer", fn); return NVH_E_NULL; }
-    if (block_size <= 0 || log_row_stride < n_rows) { set_error("%s: bad shape", fn); return NVH_E_SHAPE; }
-    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
-    return sample_rows_impl(fn, nullptr, logits, n_rows, n, stride, SampleArgs{temperatures, row_keys, nullptr, seed}, adv, dtype, stream, tr);
+    int d;
+    const AdvanceArgs adv = advance_args(&d, n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps);
+    return choose_rows("greedy_advance", nullptr, logits, n_rows, n, logits_row_stride, nullptr, nullptr, adv, d, dtype, stream);
 }
 
 int nvh_sample_rows(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
                     const float* temperatures, const uint32_t* row_keys, const int64_t* steps, uint64_t seed, int dtype, void* stream) {
-    return sample_rows_entry("sample_rows", out, logits, n_rows, n, logits_row_stride, temperatures, row_keys, steps, seed, dtype, stream, nullptr);
+    const SampleArgs s{temperatures, row_keys, steps, seed};
+    return choose_rows("sample_rows", out, logits, n_rows, n, logits_row_stride, &s, nullptr, AdvanceArgs{}, 0, dtype, stream);
 }
 
 int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row_stride,
@@ -548,15 +563,18 @@ int nvh_sample_advance(const void* logits, int n_rows, int n, int64_t logits_row
                        const int32_t* block_tables, int64_t bt_row_stride, int block_size,
                        int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
                        const float* temperatures, const uint32_t* row_keys, uint64_t seed, int dtype, void* stream) {
-    return sample_advance_entry("sample_advance", logits, n_rows, n, logits_row_stride, input_ids, positions, context_lens, slot_mapping, block_tables,
-                                bt_row_stride, block_size, tokens_log, log_row_stride, row_steps, temperatures, row_keys, seed, dtype, stream, nullptr);
+    int d;
+    const AdvanceArgs adv = advance_args(&d, n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps);
+    const SampleArgs s{temperatures, row_keys, nullptr, seed};
+    return choose_rows("sample_advance", nullptr, logits, n_rows, n, logits_row_stride, &s, nullptr, adv, d, dtype, stream);
 }
 
 int nvh_sample_rows_truncated(int64_t* out, const void* logits, int n_rows, int n, int64_t logits_row_stride,
                               const float* temperatures, const uint32_t* row_keys, const int64_t* steps,
                               const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream) {
+    const SampleArgs s{temperatures, row_keys, steps, seed};
     const Truncation tr{top_ks, top_ps};
-    return sample_rows_entry("sample_rows_truncated", out, logits, n_rows, n, logits_row_stride, temperatures, row_keys, steps, seed, dtype, stream, &tr);
+    return choose_rows("sample_rows_truncated", out, logits, n_rows, n, logits_row_stride, &s, &tr, AdvanceArgs{}, 0, dtype, stream);
 }
 
 int nvh_sample_advance_truncated(const void* logits, int n_rows, int n, int64_t logits_row_stride,
@@ -565,9 +583,11 @@ int nvh_sample_advance_truncated(const void* logits, int n_rows, int n, int64_t 
                                  int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
                                  const float* temperatures, const uint32_t* row_keys,
                                  const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream) {
+    int d;
+    const AdvanceArgs adv = advance_args(&d, n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps);
+    const SampleArgs s{temperatures, row_keys, nullptr, seed};
     const Truncation tr{top_ks, top_ps};
-    return sample_advance_entry("sample_advance_truncated", logits, n_rows, n, logits_row_stride, input_ids, positions, context_lens, slot_mapping,
-                                block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps, temperatures, row_keys, seed, dtype, stream, &tr);
+    return choose_rows("sample_advance_truncated", nullptr, logits, n_rows, n, logits_row_stride, &s, &tr, adv, d, dtype, stream);
 }
 
 int nvh_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, void* stream) {
@@ -744,41 +764,23 @@ int nvh_qkv_rope_attend_status(const void* workspace, uint32_t* timed_out) {
     return 0;
 }
 
-static int greedy_advance_candidates_impl(const float* candidate_val, const int32_t* candidate_idx, int groups, int64_t candidate_stride,
-                                  int n_rows, int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
-                                  const int32_t* block_tables, int64_t bt_row_stride, int block_size,
-                                  int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
-                                  const void* embed, int vocab, int hidden, void* hidden_out, int64_t hidden_row_stride, void* hidden_packed, void* stream) {
+// the same choice over the candidate records of a fused LM head (fn: the entry point; dtype: the embedding table's)
+static int choose_candidates(const char* fn, const float* candidate_val, const int32_t* candidate_idx, int groups, int64_t candidate_stride, int n_rows,
+                             const AdvanceArgs& adv, int adv_defect, int vocab, int dtype, void* stream) {
     if (n_rows == 0) return 0;
-    if (!candidate_val || !candidate_idx || !input_ids || !positions || !context_lens || !slot_mapping || !block_tables || !tokens_log || !row_steps) {
-        set_error("greedy_advance_candidates: null pointer");
-        return NVH_E_NULL;
-    }
-    if (n_rows < 0 || groups <= 0 || candidate_stride < n_rows || block_size <= 0 || log_row_stride < n_rows) { set_error("greedy_advance_candidates: bad shape"); return NVH_E_SHAPE; }
-    AdvanceArgs adv{input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps};
-    if (embed) {
-        if (!hidden_out) { set_error("greedy_advance_candidates_embed: null pointer"); return NVH_E_NULL; }
-        if (vocab <= 0) { set_error("greedy_advance_candidates_embed: vocab %d", vocab); return NVH_E_SHAPE; }
-        if (hidden <= 0 || hidden % 32 != 0 || hidden_row_stride < hidden || hidden_row_stride % 8 != 0) {
-            set_error("greedy_advance_candidates_embed: hidden=%d must be a multiple of 32, row stride %lld a multiple of 8 and >= hidden", hidden, (long long)hidden_row_stride);
-            return NVH_E_SHAPE;
-        }
-        if (!aligned16(embed) || !aligned16(hidden_out) || (hidden_packed && !aligned16(hidden_packed))) {
-            set_error("greedy_advance_candidates_embed: embed / hidden_out / hidden_packed must be 16-byte aligned");
-            return NVH_E_ALIGN;
-        }
-        adv.embed = (const uint16_t*)embed; adv.hidden = hidden; adv.hidden_out = (uint16_t*)hidden_out;
-        adv.hidden_stride = hidden_row_stride; adv.hidden_packed = (uint16_t*)hidden_packed;
-    }
-    return launch_argmax_candidates(candidate_val, candidate_idx, groups, candidate_stride, n_rows, embed ? vocab : 0x7fffffff, adv, (hipStream_t)stream);
+    if (dtype != NVH_BF16) return defect(fn, NVH_E_DTYPE);
+    if (!candidate_val || !candidate_idx || adv_defect == NVH_E_NULL) return defect(fn, NVH_E_NULL);
+    if (n_rows < 0 || groups <= 0 || candidate_stride < n_rows || adv_defect == NVH_E_SHAPE) return defect(fn, NVH_E_SHAPE);
+    if (adv_defect) return defect(fn, adv_defect);
+    return launch_argmax_candidates(candidate_val, candidate_idx, groups, candidate_stride, n_rows, vocab, adv, (hipStream_t)stream);
 }
 int nvh_greedy_advance_candidates(const float* candidate_val, const int32_t* candidate_idx, int groups, int64_t candidate_stride,
                                   int n_rows, int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
                                   const int32_t* block_tables, int64_t bt_row_stride, int block_size,
                                   int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps, void* stream) {
-    return greedy_advance_candidates_impl(candidate_val, candidate_idx, groups, candidate_stride, n_rows, input_ids, positions, context_lens,
-                                          slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps,
-                                          nullptr, 0, 0, nullptr, 0, nullptr, stream);
+    int d;
+    const AdvanceArgs adv = advance_args(&d, n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps);
+    return choose_candidates("greedy_advance_candidates", candidate_val, candidate_idx, groups, candidate_stride, n_rows, adv, d, 0x7fffffff, NVH_BF16, stream);
 }
 int nvh_greedy_advance_candidates_embed(const float* candidate_val, const int32_t* candidate_idx, int groups, int64_t candidate_stride,
                                         int n_rows, int64_t* input_ids, int64_t* positions, int32_t* context_lens, int32_t* slot_mapping,
@@ -786,12 +788,10 @@ int nvh_greedy_advance_candidates_embed(const float* candidate_val, const int32_
                                         int64_t* tokens_log, int64_t log_row_stride, int64_t* row_steps,
                                         const void* embed_weight, int vocab, int hidden, void* hidden_out, int64_t hidden_row_stride, void* hidden_packed,
                                         int dtype, void* stream) {
-    if (n_rows == 0) return 0;
-    if (dtype != NVH_BF16) { set_error("greedy_advance_candidates_embed: dtype %d not supported (bf16 only)", dtype); return NVH_E_DTYPE; }
-    if (!embed_weight) { set_error("greedy_advance_candidates_embed: null pointer"); return NVH_E_NULL; }
-    return greedy_advance_candidates_impl(candidate_val, candidate_idx, groups, candidate_stride, n_rows, input_ids, positions, context_lens,
-                                          slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps,
-                                          embed_weight, vocab, hidden, hidden_out, hidden_row_stride, hidden_packed, stream);
+    int d;
+    const EmbedLookup e{embed_weight, vocab, hidden, hidden_out, hidden_row_stride, hidden_packed};
+    const AdvanceArgs adv = advance_args(&d, n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, bt_row_stride, block_size, tokens_log, log_row_stride, row_steps, &e);
+    return choose_candidates("greedy_advance_candidates_embed", candidate_val, candidate_idx, groups, candidate_stride, n_rows, adv, d, vocab, dtype, stream);
 }
 int64_t nvh_pack_index(int row, int col, int cols) { return pack_index(row, col, cols); }
 

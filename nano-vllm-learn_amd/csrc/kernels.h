@@ -99,24 +99,9 @@ struct AdvanceArgs {             // all null: plain argmax
     int64_t hidden_stride;
     uint16_t* hidden_packed;     // nullable
 };
-#ifdef __HIPCC__
-// scheduler.postprocess (append the token) + prepare_decode for the NEXT step (engine/model_runner.py:244-269), on the device:
-// the row's workgroup owns the row's metadata, so there is nothing to synchronise
-__device__ __forceinline__ void advance_row(const AdvanceArgs& adv, int row, int token) {
-    const int ctx = adv.context_lens[row];
-    if (ctx > 0) {                                             // padding rows (ctx 0, slot -1) stay as they are
-        adv.tokens_log[adv.row_steps[row] * adv.log_stride + row] = token;
-        adv.row_steps[row] += 1;
-        adv.input_ids[row] = token;
-        adv.positions[row] += 1;
-        adv.context_lens[row] = ctx + 1;
-        const int last = ctx;                                  // index of the token the next step stores: new_ctx - 1
-        adv.slot_mapping[row] = adv.block_tables[row * adv.bt_stride + last / adv.block_size] * adv.block_size + last % adv.block_size;
-    }
-}
-#endif
+// sample.hip: the greedy token of each row of materialised logits; the advance itself (advance_row) is token_choice.h's
 int launch_argmax_rows(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const AdvanceArgs& adv, hipStream_t stream);
-// sample.hip: temperature sampling of materialised logits (s.steps null: the counter is adv.row_steps) and the bare noise
+// temperature sampling of the same (s.steps null: the counter is adv.row_steps) and the bare noise
 int launch_sample_rows(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const SampleArgs& s, const AdvanceArgs& adv, hipStream_t stream);
 int launch_gumbel_noise(float* out, uint64_t seed, uint32_t row_key, uint64_t step, int n, hipStream_t stream);
 // sample_truncated.hip: the same over the top-k / top-p value classes of each row (top_ks int32 [rows], top_ps float [rows])

@@ -8,6 +8,7 @@
 //   out = bf16( float(bf16(x32 * rsqrt(var + eps))) * float(weight) )          (layernorm.py:35-40)
 #include "common.h"
 #include "kernels.h"
+#include "token_choice.h"
 
 namespace nvh {
 
@@ -124,71 +125,41 @@ __global__ __launch_bounds__(256) void residual_add_pack_kernel(uint16_t* __rest
     }
 }
 
-// Greedy sampling: argmax over each row of bf16 logits (nanovllm/layers/sampler.py at temperature 0 reduces to this).
-// One 1024-thread workgroup per row streams the row with 16-byte loads; ties resolve to the lowest index.
 // Final step of the fused lm_head + argmax: per row, the best of `groups` candidates (value desc, column asc), then the
 // advance bookkeeping.  One 256-thread workgroup per row.
 __global__ __launch_bounds__(256) void argmax_candidates_kernel(const float* __restrict__ cand_val, const int32_t* __restrict__ cand_idx,
                                                                  int groups, int64_t cand_stride, int vocab, const AdvanceArgs adv) {
-    __shared__ float lds_v[4];
-    __shared__ int lds_i[4];
+    __shared__ ArgmaxFold<4> fold;
     const int row = blockIdx.x;
-    // the row's metadata travels under the candidate loads (thread 0 owns it): the bookkeeping behind the arg-max is then stores only,
+    // the row's metadata travels under the candidate loads: the bookkeeping behind the arg-max is then stores only (thread 0's),
     // and they are issued AFTER the embedding row's loads, so that the two dependent chains of the tail (token -> embedding row,
     // context -> block table -> slot) overlap instead of following each other
-    int m_ctx = 0, m_blk = 0;
-    int64_t m_steps = 0, m_pos = 0, m_tok = 0;
-    if (threadIdx.x == 0) {
-        m_ctx = adv.context_lens[row];
-        m_steps = adv.row_steps[row];
-        m_pos = adv.positions[row];
-        m_tok = adv.input_ids[row];
-        if (m_ctx > 0) m_blk = adv.block_tables[row * adv.bt_stride + m_ctx / adv.block_size];
-    }
+    const RowMeta meta = load_row_meta(adv, row);
     float best = -INFINITY;
-    int bidx = 0x7fffffff;
+    int bidx = kNoColumn;
     for (int gi = threadIdx.x; gi < groups; gi += 256) {
         const float v = cand_val[(int64_t)gi * cand_stride + row];
         const int i = cand_idx[(int64_t)gi * cand_stride + row];
         if (argmax_better(v, i, best, bidx)) { best = v; bidx = i; }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bidx, off, 64);
-        if (argmax_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { lds_v[threadIdx.x >> 6] = best; lds_i[threadIdx.x >> 6] = bidx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (argmax_better(lds_v[w], lds_i[w], best, bidx)) { best = lds_v[w]; bidx = lds_i[w]; }
-        // a valid token whatever the candidates held (the index feeds an embedding-row address below): the ordering above never
-        // lets the (-inf, INT_MAX) identity survive a real candidate; the clamp covers corrupt candidate indices as well
-        bidx = bidx < 0 ? 0 : (bidx >= vocab ? vocab - 1 : bidx);
-        if (adv.embed) lds_i[0] = m_ctx > 0 ? bidx : (int)m_tok;             // padding rows keep their token
-    }
+    block_argmax(best, bidx, fold);
+    // a valid token whatever the candidates held (the index feeds an embedding-row address below): the ordering above never
+    // lets the (-inf, kNoColumn) identity survive a real candidate; the clamp covers corrupt candidate indices as well
+    bidx = bidx < 0 ? 0 : (bidx >= vocab ? vocab - 1 : bidx);
     constexpr int EMB = 4;                                                   // 16-byte chunks of the embedding row per thread: hidden <= 8192
     u32x4 ev[EMB];
     const uint16_t* src = nullptr;
     if (adv.embed) {
         // the next step's embedding lookup (layers/embed_head.py:34-45 at tp = 1) by the workgroup that has just chosen the token
-        __syncthreads();
-        src = adv.embed + (int64_t)lds_i[0] * adv.hidden;
+        // (every thread holds the fold's result); padding rows keep their token
+        src = adv.embed + (int64_t)(meta.ctx > 0 ? bidx : (int)meta.tok) * adv.hidden;
 #pragma unroll
         for (int u = 0; u < EMB; ++u) {
             const int c = (threadIdx.x + 256 * u) * 8;
             if (c < adv.hidden) ev[u] = *reinterpret_cast<const u32x4*>(src + c);
         }
     }
-    if (threadIdx.x == 0 && m_ctx > 0) {                                     // advance_row from the prefetched metadata: stores only
-        adv.tokens_log[m_steps * adv.log_stride + row] = bidx;
-        adv.row_steps[row] = m_steps + 1;
-        adv.input_ids[row] = bidx;
-        adv.positions[row] = m_pos + 1;
-        adv.context_lens[row] = m_ctx + 1;
-        adv.slot_mapping[row] = m_blk * adv.block_size + m_ctx % adv.block_size;
-    }
+    if (threadIdx.x == 0) store_row_advance(adv, row, meta, bidx);
     if (adv.embed) {
 #pragma unroll
         for (int u = 0; u < EMB; ++u) {
@@ -207,53 +178,7 @@ __global__ __launch_bounds__(256) void argmax_candidates_kernel(const float* __r
     }
 }
 
-__global__ __launch_bounds__(1024) void argmax_rows_kernel(int64_t* __restrict__ out, const uint16_t* __restrict__ x, int n, int64_t stride,
-                                                            const AdvanceArgs adv) {
-    __shared__ float lds_v[16];
-    __shared__ int lds_i[16];
-    const uint16_t* row = x + blockIdx.x * stride;
-    float best = -INFINITY;
-    int bidx = 0x7fffffff;
-    const int chunks = n / 8;
-    for (int c = threadIdx.x; c < chunks; c += 1024) {
-        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c * 8));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float lo = bf16_lo(v[k]), hi = bf16_hi(v[k]);
-            if (argmax_better(lo, c * 8 + 2 * k, best, bidx)) { best = lo; bidx = c * 8 + 2 * k; }
-            if (argmax_better(hi, c * 8 + 2 * k + 1, best, bidx)) { best = hi; bidx = c * 8 + 2 * k + 1; }
-        }
-    }
-    for (int i = chunks * 8 + threadIdx.x; i < n; i += 1024) {              // tail when n % 8 != 0
-        const float f = bf16_lo((uint32_t)row[i]);
-        if (argmax_better(f, i, best, bidx)) { best = f; bidx = i; }
-    }
-    // wave reduce (torch.argmax order: NaN first, value desc, index asc), then across the 16 waves
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bidx, off, 64);
-        if (argmax_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { lds_v[wave] = best; lds_i[wave] = bidx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (argmax_better(lds_v[w], lds_i[w], best, bidx)) { best = lds_v[w]; bidx = lds_i[w]; }
-        bidx = bidx < 0 ? 0 : (bidx >= n ? n - 1 : bidx);             // n >= 1 (host): always a valid column
-        if (out) out[blockIdx.x] = bidx;
-        if (adv.input_ids) advance_row(adv, blockIdx.x, bidx);
-    }
-}
-
 }  // namespace
-
-int launch_argmax_rows(int64_t* out, const void* x, int n_rows, int n, int64_t stride, const AdvanceArgs& adv, hipStream_t stream) {
-    if (n_rows == 0) return 0;
-    hipLaunchKernelGGL(argmax_rows_kernel, dim3(n_rows), dim3(1024), 0, stream, out, (const uint16_t*)x, n, stride, adv);
-    return check_launch("argmax_rows");
-}
 
 int launch_residual_add_pack(void* residual, const void* y, void* packed, int n_rows, int hidden, int64_t res_stride, int64_t y_stride,
                              hipStream_t stream) {

@@ -7,19 +7,20 @@
 //   * pass 1  arg-max in torch.argmax's order: the greedy token of a T <= 0 row, the lowest NaN column of a NaN row, the row maximum
 //     pass 2  top-k on: column counts per bin; suffix scan -> the bin of v_k          pass 3  its 16 sub-bins -> key(v_k)
 //     pass 4  top-p on: weights of the top-k survivors per bin; scan vs top_p * Z     pass 5  its 16 sub-bins -> key(v_p)
-//     final   Philox / Gumbel / fma for columns with key >= max(key(v_k), key(v_p)) only, arg-max fold, advance_row
+//     final   Philox / Gumbel / fma for columns with key >= max(key(v_k), key(v_p)) only, arg-max fold, finish_row
 //   * determinism: a weight is the INTEGER round(w * 2^40), w = exp((l - max) / T) in [0, 1], added with integer LDS atomics
 //     (associative: the sums do not depend on the order of arrival; n <= 2^18 columns keep every sum below 2^58), scanned in a
 //     fixed order and compared with top_p * Z in fp64.  No floating-point atomic, no order-dependent float sum.
 //   * LDS: 4096 x uint32 counts (16 KB) + 4096 x uint64 weights (32 KB) + 16 + 16 sub-bins and the folds' scratch: 48.5 KB
 #include "common.h"
 #include "kernels.h"
+#include "token_choice.h"
 
 namespace nvh {
 
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kRowThreads;
 constexpr int kBins = 4096;                     // key >> 4
 constexpr int kPerThread = kBins / kThreads;    // consecutive bins a thread scans
 constexpr float kWeightOne = 0x1p40f;           // fixed point of a weight
@@ -38,50 +39,12 @@ __device__ __forceinline__ uint64_t fixed_weight(uint32_t bits, float row_max, f
     return (uint64_t)__builtin_rintf(w * kWeightOne);
 }
 
-// f(column, bf16 bits) for every column of the row: 8 per 16-byte load, a column per thread in the n % 8 tail
-template <typename F>
-__device__ __forceinline__ void for_columns(const uint16_t* __restrict__ row, int n, F&& f) {
-    constexpr int kAhead = 4;       // loads in flight per thread: a pass waits for its loads' latency (19 round trips at 151936), not for their bytes
-    const int chunks = n / 8;
-    for (int c0 = threadIdx.x; c0 < chunks; c0 += kAhead * kThreads) {
-        u32x4 v[kAhead];
-#pragma unroll
-        for (int u = 0; u < kAhead; ++u)
-            if (c0 + u * kThreads < chunks) v[u] = *reinterpret_cast<const u32x4*>(row + (c0 + u * kThreads) * 8);
-#pragma unroll
-        for (int u = 0; u < kAhead; ++u) {
-            const int c = c0 + u * kThreads;
-            if (c >= chunks) break;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { f(c * 8 + 2 * k, v[u][k] & 0xFFFFu); f(c * 8 + 2 * k + 1, v[u][k] >> 16); }
-        }
-    }
-    for (int i = chunks * 8 + threadIdx.x; i < n; i += kThreads) f(i, (uint32_t)row[i]);
-}
-
 struct Fold {                       // LDS scratch of the workgroup-wide folds
-    float v[16];
-    int i[16];
+    ArgmaxFold<16> arg;
     uint64_t wave_sum[16];
     uint64_t total, above;
     int bin;
 };
-
-// arg-max over the workgroup (NaN first, value desc, column asc), the result in every thread
-__device__ __forceinline__ void block_argmax(float& best, int& bidx, Fold& f) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bidx, off, 64);
-        if (argmax_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
-    }
-    __syncthreads();                                                        // the previous fold's readers are done
-    if ((threadIdx.x & 63) == 0) { f.v[threadIdx.x >> 6] = best; f.i[threadIdx.x >> 6] = bidx; }
-    __syncthreads();
-    best = f.v[0]; bidx = f.i[0];
-    for (int w = 1; w < 16; ++w)
-        if (argmax_better(f.v[w], f.i[w], best, bidx)) { best = f.v[w]; bidx = f.i[w]; }
-}
 
 struct Cut { int bin; uint64_t above; double target; };   // bin -1: no bin qualifies
 
@@ -142,18 +105,16 @@ __global__ __launch_bounds__(1024) void sample_truncated_kernel(int64_t* __restr
     __shared__ Fold fold;
     const int r = blockIdx.x;
     const uint16_t* row = x + r * stride;
-    const float temp = s.temperatures[r];
-    const uint32_t rkey = s.row_keys[r];
-    const uint64_t step = (uint64_t)(s.steps ? s.steps[r] : adv.row_steps[r]);
+    const RowNoise z = row_noise(s, adv, r);
+    const float temp = z.temp;
+    // a pass over the row's columns: the row (<= 300 KB) comes from the cache, four ordinary 16-byte loads in flight per thread
+    const auto each_column = [&](auto&& f) { for_columns<4, false>(row, n, f); };
 
     // pass 1: the greedy arg-max
     float best = -INFINITY;
-    int bidx = 0x7fffffff;
-    for_columns(row, n, [&](int col, uint32_t bits) {
-        const float f = bf16_lo(bits);
-        if (argmax_better(f, col, best, bidx)) { best = f; bidx = col; }
-    });
-    block_argmax(best, bidx, fold);
+    int bidx = kNoColumn;
+    each_column([&](int col, uint32_t bits) { argmax_column(col, bits, best, bidx); });
+    block_argmax(best, bidx, fold.arg);
 
     if (temp > 0.f && best == best) {                                       // workgroup-uniform; a NaN row keeps its lowest NaN column
         const float row_max = best;
@@ -168,11 +129,11 @@ __global__ __launch_bounds__(1024) void sample_truncated_kernel(int64_t* __restr
             for (int j = 0; j < kPerThread; ++j) cnt[threadIdx.x * kPerThread + j] = 0;
             if (threadIdx.x < 16) sub_cnt[threadIdx.x] = 0;
             __syncthreads();
-            for_columns(row, n, [&](int, uint32_t bits) { atomicAdd(&cnt[order_key(bits) >> 4], 1u); });
+            each_column([&](int, uint32_t bits) { atomicAdd(&cnt[order_key(bits) >> 4], 1u); });
             __syncthreads();
             const Cut c = find_cut(cnt, (double)top_k, false, fold);         // 1 <= k < n: a bin always qualifies
             // pass 3: that bin's 16 values
-            for_columns(row, n, [&](int, uint32_t bits) {
+            each_column([&](int, uint32_t bits) {
                 const uint32_t key = order_key(bits);
                 if ((int)(key >> 4) == c.bin) atomicAdd(&sub_cnt[key & 15], 1u);
             });
@@ -186,7 +147,7 @@ __global__ __launch_bounds__(1024) void sample_truncated_kernel(int64_t* __restr
             for (int j = 0; j < kPerThread; ++j) wgt[threadIdx.x * kPerThread + j] = 0;
             if (threadIdx.x < 16) sub_wgt[threadIdx.x] = 0;
             __syncthreads();
-            for_columns(row, n, [&](int, uint32_t bits) {
+            each_column([&](int, uint32_t bits) {
                 const uint32_t key = order_key(bits);
                 if (key < key_k) return;
                 const uint64_t w = fixed_weight(bits, row_max, scale);
@@ -195,7 +156,7 @@ __global__ __launch_bounds__(1024) void sample_truncated_kernel(int64_t* __restr
             __syncthreads();
             const Cut c = find_cut(wgt, (double)top_p, true, fold);
             // pass 5: that bin's 16 values
-            for_columns(row, n, [&](int, uint32_t bits) {
+            each_column([&](int, uint32_t bits) {
                 const uint32_t key = order_key(bits);
                 if ((int)(key >> 4) != c.bin || key < key_k) return;
                 const uint64_t w = fixed_weight(bits, row_max, scale);
@@ -209,41 +170,17 @@ __global__ __launch_bounds__(1024) void sample_truncated_kernel(int64_t* __restr
         uint32_t thr = key_k > key_p ? key_k : key_p;
         thr = thr < key_max ? thr : key_max;                                // the largest class is always kept
 
-        // final pass: the perturbed arg-max of sample_rows_kernel over the kept columns; four columns share a Philox call
+        // final pass: the perturbed arg-max of sample_rows_kernel over the kept columns
+        const auto kept = [thr](uint32_t bits) { return order_key(bits) >= thr; };
         best = -INFINITY;
-        bidx = 0x7fffffff;
-        const int chunks = n / 8;
-        for (int c = threadIdx.x; c < chunks; c += kThreads) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(row + c * 8);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t bits[4] = {v[2 * h] & 0xFFFFu, v[2 * h] >> 16, v[2 * h + 1] & 0xFFFFu, v[2 * h + 1] >> 16};
-                bool keep[4], any = false;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { keep[k] = order_key(bits[k]) >= thr; any |= keep[k]; }
-                if (!any) continue;
-                uint32_t w[4];
-                sample_bits4(s.seed, rkey, step, (uint32_t)(c * 8 + 4 * h), w);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float sc = sample_score(bf16_lo(bits[k]), temp, gumbel_from_bits(w[k]));
-                    if (keep[k] && argmax_better(sc, c * 8 + 4 * h + k, best, bidx)) { best = sc; bidx = c * 8 + 4 * h + k; }
-                }
-            }
-        }
-        for (int i = chunks * 8 + threadIdx.x; i < n; i += kThreads) {
-            const uint32_t bits = row[i];
-            if (order_key(bits) < thr) continue;
-            const float sc = sample_score(bf16_lo(bits), temp, sample_gumbel(s.seed, rkey, step, (uint32_t)i));
-            if (argmax_better(sc, i, best, bidx)) { best = sc; bidx = i; }
-        }
-        block_argmax(best, bidx, fold);
+        bidx = kNoColumn;
+        walk_row<1, false>(row, n,
+            [&](int col0, const u32x4& v) { perturbed_argmax_chunk(z, col0, v, kept, best, bidx); },
+            [&](int col, uint32_t bits) { perturbed_argmax_column(z, col, bits, kept, best, bidx); });
+        __syncthreads();                                                    // pass 1's fold has been read by every thread
+        block_argmax(best, bidx, fold.arg);
     }
-    if (threadIdx.x == 0) {
-        bidx = bidx < 0 ? 0 : (bidx >= n ? n - 1 : bidx);                   // n >= 1 (host): always a valid column
-        if (out) out[r] = bidx;
-        if (adv.input_ids) advance_row(adv, r, bidx);
-    }
+    if (threadIdx.x == 0) finish_row(out, adv, r, n, bidx);
 }
 
 }  // namespace

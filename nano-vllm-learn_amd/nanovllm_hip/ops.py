@@ -544,40 +544,50 @@ def linear_candidate_groups(n, k) -> int:
     return int(_lib.load().nvh_linear_small_m_candidate_groups(n, k))
 
 
+def _logits_args(logits):
+    """The checks every entry point makes on bf16 logits [M, N], and their argument run (pointer, M, N, row stride)."""
+    _require_gpu_bf16(logits=logits)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    return logits.data_ptr(), logits.shape[0], logits.shape[1], logits.stride(0)
+
+
+def _advance_args(m, input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps):
+    """The checks on a decode session's metadata tensors (m rows), and the advance argument run of the C ABI."""
+    _require_i32(context_lens=context_lens, slot_mapping=slot_mapping, block_tables=block_tables)
+    for t in (input_ids, positions, tokens_log, row_steps):
+        assert t.dtype == torch.int64 and t.is_cuda
+    assert block_tables.stride(1) == 1
+    assert tokens_log.dim() == 2 and tokens_log.shape[1] >= m and tokens_log.stride(1) == 1
+    return (input_ids.data_ptr(), positions.data_ptr(), context_lens.data_ptr(), slot_mapping.data_ptr(), block_tables.data_ptr(),
+            block_tables.stride(0), block_size, tokens_log.data_ptr(), tokens_log.stride(0), row_steps.data_ptr())
+
+
+def _call(name, *args):
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
 def greedy_advance_candidates(cand_val, cand_idx, groups, n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, block_size,
                               tokens_log, row_steps, embed=None):
     """greedy_advance on the candidate records of fused_linear(candidates=...) instead of logits.
     embed = (weight [vocab, hidden], hidden_out [n_rows, hidden], hidden_packed or None): the same launch also looks up the
     chosen tokens' embedding rows for the next step (row-major and, optionally, in fragment order)."""
-    _require_i32(context_lens=context_lens, slot_mapping=slot_mapping, block_tables=block_tables)
-    for t in (input_ids, positions, tokens_log, row_steps):
-        assert t.dtype == torch.int64 and t.is_cuda
-    if embed is not None:
-        w, hid, packed = embed
-        _require_gpu_bf16(embed_weight=w, hidden_out=hid)
-        assert w.is_contiguous() and hid.shape == (n_rows, w.shape[1]) and hid.stride(1) == 1
-        assert packed is None or (packed.dtype == torch.bfloat16 and packed.is_cuda and packed.numel() >= ((n_rows + 15) // 16) * 16 * w.shape[1])
-        rc = _lib.load().nvh_greedy_advance_candidates_embed(
-            cand_val.data_ptr(), cand_idx.data_ptr(), groups, cand_val.stride(0), n_rows, input_ids.data_ptr(), positions.data_ptr(),
-            context_lens.data_ptr(), slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0), block_size,
-            tokens_log.data_ptr(), tokens_log.stride(0), row_steps.data_ptr(), w.data_ptr(), w.shape[0], w.shape[1], hid.data_ptr(), hid.stride(0),
-            None if packed is None else packed.data_ptr(), NVH_BF16, _stream())
-        _lib.check(rc, "nvh_greedy_advance_candidates_embed")
-        return
-    rc = _lib.load().nvh_greedy_advance_candidates(cand_val.data_ptr(), cand_idx.data_ptr(), groups, cand_val.stride(0), n_rows,
-                                                   input_ids.data_ptr(), positions.data_ptr(), context_lens.data_ptr(), slot_mapping.data_ptr(),
-                                                   block_tables.data_ptr(), block_tables.stride(0), block_size, tokens_log.data_ptr(),
-                                                   tokens_log.stride(0), row_steps.data_ptr(), _stream())
-    _lib.check(rc, "nvh_greedy_advance_candidates")
+    args = (cand_val.data_ptr(), cand_idx.data_ptr(), groups, cand_val.stride(0), n_rows,
+            *_advance_args(n_rows, input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps))
+    if embed is None:
+        return _call("nvh_greedy_advance_candidates", *args)
+    w, hid, packed = embed
+    _require_gpu_bf16(embed_weight=w, hidden_out=hid)
+    assert w.is_contiguous() and hid.shape == (n_rows, w.shape[1]) and hid.stride(1) == 1
+    assert packed is None or (packed.dtype == torch.bfloat16 and packed.is_cuda and packed.numel() >= ((n_rows + 15) // 16) * 16 * w.shape[1])
+    _call("nvh_greedy_advance_candidates_embed", *args, w.data_ptr(), w.shape[0], w.shape[1], hid.data_ptr(), hid.stride(0),
+          None if packed is None else packed.data_ptr(), NVH_BF16)
 
 
 def argmax_rows(logits):
     """Greedy token per row: argmax over the last dim of bf16 logits [M, N] (ties -> lowest index), int64."""
-    _require_gpu_bf16(logits=logits)
-    assert logits.dim() == 2 and logits.stride(1) == 1
+    args = _logits_args(logits)
     out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
-    rc = _lib.load().nvh_argmax_rows(out.data_ptr(), logits.data_ptr(), logits.shape[0], logits.shape[1], logits.stride(0), NVH_BF16, _stream())
-    _lib.check(rc, "nvh_argmax_rows")
+    _call("nvh_argmax_rows", out.data_ptr(), *args, NVH_BF16)
     return out
 
 
@@ -602,27 +612,26 @@ def _truncation(m, device, top_k, top_p):
     return top_k, top_p
 
 
+def _sampling_args(m, device, temperatures, row_keys, steps, seed, top_k, top_p):
+    """The one place that selects the plain or the truncated entry point: its name's suffix and its sampling argument run."""
+    _require_sampling(m, temperatures, row_keys, steps)
+    trunc = _truncation(m, device, top_k, top_p)
+    tensors = (temperatures, row_keys) + (() if steps is None else (steps,)) + (trunc or ())
+    return ("_truncated" if trunc else ""), (*(t.data_ptr() for t in tensors), int(seed) & _U64)
+
+
 def sample_rows(logits, temperatures, row_keys, steps, seed, top_k=None, top_p=None):
     """Temperature sampling per row of bf16 logits [M, N] (nvh_sample_rows): argmax_j (logits[i, j] + T_i * g) with the counter-based
     Gumbel noise g(seed, row_keys[i], steps[i], j) of csrc/sample_noise.h — the distribution of the reference's sampler.py, the greedy
     token where T_i <= 0.  temperatures float32 [M], row_keys uint32 [M], steps int64 [M] (read as uint64).  Returns int64 [M].
     top_k int32 [M] / top_p float32 [M] (either may be None = off): the arg-max runs over the top-k / top-p value classes of each row
     only (nvh_sample_rows_truncated; semantics in include/nvh_attn.h)."""
-    _require_gpu_bf16(logits=logits)
-    assert logits.dim() == 2 and logits.stride(1) == 1
+    args = _logits_args(logits)
     m = logits.shape[0]
-    _require_sampling(m, temperatures, row_keys, steps)
+    assert steps is not None
+    suffix, sampling = _sampling_args(m, logits.device, temperatures, row_keys, steps, seed, top_k, top_p)
     out = torch.empty(m, dtype=torch.int64, device=logits.device)
-    trunc = _truncation(m, logits.device, top_k, top_p)
-    if trunc is not None:
-        rc = _lib.load().nvh_sample_rows_truncated(out.data_ptr(), logits.data_ptr(), m, logits.shape[1], logits.stride(0), temperatures.data_ptr(),
-                                                   row_keys.data_ptr(), steps.data_ptr(), trunc[0].data_ptr(), trunc[1].data_ptr(),
-                                                   int(seed) & _U64, NVH_BF16, _stream())
-        _lib.check(rc, "nvh_sample_rows_truncated")
-        return out
-    rc = _lib.load().nvh_sample_rows(out.data_ptr(), logits.data_ptr(), m, logits.shape[1], logits.stride(0), temperatures.data_ptr(),
-                                     row_keys.data_ptr(), steps.data_ptr(), int(seed) & _U64, NVH_BF16, _stream())
-    _lib.check(rc, "nvh_sample_rows")
+    _call("nvh_sample_rows" + suffix, out.data_ptr(), *args, *sampling, NVH_BF16)
     return out
 
 
@@ -630,28 +639,11 @@ def sample_advance(logits, input_ids, positions, context_lens, slot_mapping, blo
                    temperatures, row_keys, seed, top_k=None, top_p=None):
     """greedy_advance with sample_rows' choice of token (nvh_sample_advance; with top_k / top_p nvh_sample_advance_truncated); the noise
     step of a row is row_steps[row] before the call increments it, so a captured step draws fresh noise on every replay."""
-    _require_gpu_bf16(logits=logits)
-    _require_i32(context_lens=context_lens, slot_mapping=slot_mapping, block_tables=block_tables)
+    args = _logits_args(logits)
     m = logits.shape[0]
-    assert logits.dim() == 2 and logits.stride(1) == 1 and block_tables.stride(1) == 1
-    for t in (input_ids, positions, tokens_log, row_steps):
-        assert t.dtype == torch.int64 and t.is_cuda
-    assert tokens_log.dim() == 2 and tokens_log.shape[1] >= m and tokens_log.stride(1) == 1
-    _require_sampling(m, temperatures, row_keys)
-    trunc = _truncation(m, logits.device, top_k, top_p)
-    if trunc is not None:
-        rc = _lib.load().nvh_sample_advance_truncated(
-            logits.data_ptr(), m, logits.shape[1], logits.stride(0), input_ids.data_ptr(), positions.data_ptr(), context_lens.data_ptr(),
-            slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0), block_size, tokens_log.data_ptr(), tokens_log.stride(0),
-            row_steps.data_ptr(), temperatures.data_ptr(), row_keys.data_ptr(), trunc[0].data_ptr(), trunc[1].data_ptr(), int(seed) & _U64,
-            NVH_BF16, _stream())
-        _lib.check(rc, "nvh_sample_advance_truncated")
-        return
-    rc = _lib.load().nvh_sample_advance(logits.data_ptr(), m, logits.shape[1], logits.stride(0), input_ids.data_ptr(), positions.data_ptr(),
-                                        context_lens.data_ptr(), slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
-                                        block_size, tokens_log.data_ptr(), tokens_log.stride(0), row_steps.data_ptr(), temperatures.data_ptr(),
-                                        row_keys.data_ptr(), int(seed) & _U64, NVH_BF16, _stream())
-    _lib.check(rc, "nvh_sample_advance")
+    advance = _advance_args(m, input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps)
+    suffix, sampling = _sampling_args(m, logits.device, temperatures, row_keys, None, seed, top_k, top_p)
+    _call("nvh_sample_advance" + suffix, *args, *advance, *sampling, NVH_BF16)
 
 
 def gumbel_noise(seed, row_key, step, n, device="cuda"):
@@ -666,14 +658,6 @@ def gumbel_noise(seed, row_key, step, n, device="cuda"):
 def greedy_advance(logits, input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps):
     """argmax_rows fused with the between-steps bookkeeping of a greedy decode session (nvh_greedy_advance): appends the
     token to `tokens_log[row_steps[r], r]` and rewrites next step's input_ids / positions / context_lens / slot_mapping in place."""
-    _require_gpu_bf16(logits=logits)
-    _require_i32(context_lens=context_lens, slot_mapping=slot_mapping, block_tables=block_tables)
-    m = logits.shape[0]
-    assert logits.dim() == 2 and logits.stride(1) == 1 and block_tables.stride(1) == 1
-    for t in (input_ids, positions, tokens_log, row_steps):
-        assert t.dtype == torch.int64 and t.is_cuda
-    assert tokens_log.dim() == 2 and tokens_log.shape[1] >= m and tokens_log.stride(1) == 1
-    rc = _lib.load().nvh_greedy_advance(logits.data_ptr(), m, logits.shape[1], logits.stride(0), input_ids.data_ptr(), positions.data_ptr(),
-                                        context_lens.data_ptr(), slot_mapping.data_ptr(), block_tables.data_ptr(), block_tables.stride(0),
-                                        block_size, tokens_log.data_ptr(), tokens_log.stride(0), row_steps.data_ptr(), NVH_BF16, _stream())
-    _lib.check(rc, "nvh_greedy_advance")
+    args = _logits_args(logits)
+    _call("nvh_greedy_advance", *args,
+          *_advance_args(logits.shape[0], input_ids, positions, context_lens, slot_mapping, block_tables, block_size, tokens_log, row_steps), NVH_BF16)

@@ -98,6 +98,78 @@ def test_argument_validation_without_gpu(lib):
     assert lib.nvh_prefill_varlen_pv16(p, p, p, p, p, p, 0, 0, 0, 0, 14, 2, 64, 896, 128, 128, 0.125, 0, 0, None, 0, None) == 0   # empty batch
 
 
+# ---- the eight token-choice entry points: one argument table, defects by argument name
+_E_DTYPE, _E_SHAPE, _E_STRIDE, _E_NULL, _E_ALIGN = -1, -2, -3, -5, -6
+_ADVANCE = ["input_ids", "positions", "context_lens", "slot_mapping", "block_tables", "bt_stride", "block_size", "tokens_log", "log_stride", "row_steps"]
+_LOGITS = ["logits", "n_rows", "n", "stride"]
+_CANDS = ["cand_val", "cand_idx", "groups", "cand_stride", "n_rows"]
+_EMBED = ["embed_weight", "vocab", "hidden", "hidden_out", "hidden_stride", "hidden_packed"]
+TOKEN_CHOICE_ARGS = {
+    "argmax_rows": ["out", *_LOGITS, "dtype", "stream"],
+    "greedy_advance": [*_LOGITS, *_ADVANCE, "dtype", "stream"],
+    "sample_rows": ["out", *_LOGITS, "temperatures", "row_keys", "steps", "seed", "dtype", "stream"],
+    "sample_advance": [*_LOGITS, *_ADVANCE, "temperatures", "row_keys", "seed", "dtype", "stream"],
+    "sample_rows_truncated": ["out", *_LOGITS, "temperatures", "row_keys", "steps", "top_ks", "top_ps", "seed", "dtype", "stream"],
+    "sample_advance_truncated": [*_LOGITS, *_ADVANCE, "temperatures", "row_keys", "top_ks", "top_ps", "seed", "dtype", "stream"],
+    "greedy_advance_candidates": [*_CANDS, *_ADVANCE, "stream"],
+    "greedy_advance_candidates_embed": [*_CANDS, *_ADVANCE, *_EMBED, "dtype", "stream"],
+}
+_SCALARS = dict(n_rows=4, n=64, stride=64, bt_stride=4, block_size=256, log_stride=4, seed=11, dtype=0, stream=None, groups=8, cand_stride=64,
+                vocab=1000, hidden=896, hidden_stride=896)
+_POINTERS = ("out", "logits", "temperatures", "row_keys", "steps", "top_ks", "top_ps", "cand_val", "cand_idx", "embed_weight", "hidden_out", "hidden_packed",
+             "input_ids", "positions", "context_lens", "slot_mapping", "block_tables", "tokens_log", "row_steps")
+# one defect per call: (argument, bad value or "null" / "misaligned", code); a row applies to every entry point that has the argument
+ONE_DEFECT = [("dtype", 7, _E_DTYPE)] + \
+             [(p, "null", _E_NULL) for p in _POINTERS if p != "hidden_packed"] + \
+             [("n", 0, _E_SHAPE), ("n", -3, _E_SHAPE), ("block_size", 0, _E_SHAPE), ("block_size", -1, _E_SHAPE), ("log_stride", 3, _E_SHAPE),
+              ("stride", 68, _E_STRIDE), ("stride", 56, _E_STRIDE), ("logits", "misaligned", _E_ALIGN)]
+# two defects per call: dtype, null pointers, shape, stride, alignment, in that order, at every entry point
+# (the last column: the code before the entry points shared one path, where it was another)
+TWO_DEFECTS = [
+    ("greedy_advance", {"positions": "null", "n": 0}, _E_NULL, None),
+    ("sample_rows", {"n": 0, "stride": 68}, _E_SHAPE, None),
+    ("argmax_rows", {"stride": 68, "logits": "misaligned"}, _E_STRIDE, None),
+    ("sample_rows_truncated", {"top_ps": "null", "logits": "misaligned"}, _E_NULL, None),
+    ("sample_advance", {"dtype": 7, "input_ids": "null"}, _E_DTYPE, _E_NULL),
+    ("sample_advance", {"block_size": 0, "logits": "null"}, _E_NULL, _E_SHAPE),
+    ("sample_advance_truncated", {"dtype": 7, "log_stride": 3}, _E_DTYPE, _E_SHAPE),
+    ("greedy_advance_candidates_embed", {"groups": 0, "hidden_out": "null"}, _E_NULL, _E_SHAPE),
+]
+
+
+def _token_choice_call(lib, entry, defects):
+    buf = (ctypes.c_char * 4096)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    vals = {**_SCALARS, **{name: p for name in _POINTERS}}
+    for name, bad in defects.items():
+        vals[name] = {"null": None, "misaligned": p + 2}.get(bad, bad) if isinstance(bad, str) else bad
+    rc = getattr(lib, "nvh_" + entry)(*[vals[a] for a in TOKEN_CHOICE_ARGS[entry]])
+    return rc, lib.nvh_last_error().decode()
+
+
+def _error_label(entry):
+    return "greedy_advance_candidates" if entry == "greedy_advance_candidates_embed" else entry   # the two share their checks' messages
+
+
+@pytest.mark.parametrize("entry", list(TOKEN_CHOICE_ARGS))
+def test_token_choice_entry_points_report_one_defect(lib, entry):
+    args = TOKEN_CHOICE_ARGS[entry]
+    assert set(args) <= set(_SCALARS) | set(_POINTERS)
+    rows = [(a, bad, code) for a, bad, code in ONE_DEFECT if a in args]
+    assert {code for _, _, code in rows} >= ({_E_NULL, _E_SHAPE} if "logits" not in args else {_E_DTYPE, _E_NULL, _E_SHAPE, _E_STRIDE, _E_ALIGN})
+    for arg, bad, code in rows:
+        rc, msg = _token_choice_call(lib, entry, {arg: bad})
+        assert rc == code, f"nvh_{entry}({arg}={bad}): {rc}, expected {code} ({msg})"
+        assert _error_label(entry) in msg, f"nvh_{entry}({arg}={bad}): the message does not name the entry point: {msg}"
+    assert _token_choice_call(lib, entry, {"n_rows": 0, "dtype": 7, "logits": "null", "input_ids": "null", "cand_val": "null"})[0] == 0   # zero rows: before any check
+
+
+@pytest.mark.parametrize("entry,defects,code,code_before", TWO_DEFECTS)
+def test_token_choice_entry_points_share_one_precedence(lib, entry, defects, code, code_before):
+    rc, msg = _token_choice_call(lib, entry, defects)
+    assert rc == code and _error_label(entry) in msg, f"nvh_{entry}({defects}): {rc}, expected {code} ({msg})"
+
+
 def test_ops_refuse_cpu_tensors():
     """No CPU fallback: the product path must fail loudly off-GPU."""
     from nanovllm_hip import ops

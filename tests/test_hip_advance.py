@@ -49,7 +49,19 @@ def test_initial_state_comes_from_the_product_producer(golden):
         assert np.array_equal(m[key].numpy(), g[f"traj_{key}"][0])
 
 
-@pytest.mark.parametrize("form", ["logits", "candidates", "candidates_embed"])
+def _advance_from_logits(ops, form, logits, *state):
+    """One advance through the logits entry point of `form`: greedy, or sampled at temperature 0 in every row (plain / truncated)."""
+    if form == "logits":
+        return ops.greedy_advance(logits, *state)
+    m, dev = logits.shape[0], logits.device
+    trunc = dict(top_k=torch.full((m,), 20, dtype=torch.int32, device=dev), top_p=torch.full((m,), 0.8, device=dev)) if form == "truncated_T0" else {}
+    ops.sample_advance(logits, *state, torch.zeros(m, device=dev), torch.arange(m, dtype=torch.int32, device=dev), 5, **trunc)
+
+
+LOGITS_FORMS = ["logits", "sampled_T0", "truncated_T0"]
+
+
+@pytest.mark.parametrize("form", [*LOGITS_FORMS, "candidates", "candidates_embed"])
 def test_device_advance_follows_reference_trajectory(golden, form):
     from nanovllm_hip import ops
     g = golden("meta_runner.npz")
@@ -58,7 +70,7 @@ def test_device_advance_follows_reference_trajectory(golden, form):
     steps = g["traj_input_ids"].shape[0]
     toks = g["traj_tokens"]
     hidden, groups = 64, 5
-    if form == "logits":
+    if form in LOGITS_FORMS:
         logits = torch.zeros(n, VOCAB, dtype=torch.bfloat16, device=dev)
     else:
         cand_val = torch.zeros(groups, 64, dtype=torch.float32, device=dev)
@@ -71,11 +83,11 @@ def test_device_advance_follows_reference_trajectory(golden, form):
     for i in range(steps - 1):
         _check_step(g, st, i, form)                              # what step i's attention call would be fed
         nxt = torch.from_numpy(toks[i + 1]).to(dev)              # the token "sampled" at step i (postprocess appends it)
-        if form == "logits":
+        if form in LOGITS_FORMS:
             logits.zero_()
             logits[rows, nxt] = 1.0
-            ops.greedy_advance(logits, st["input_ids"], st["positions"], st["context_lens"], st["slot_mapping"], st["block_tables"], 256,
-                               st["tokens"], st["row_steps"])
+            _advance_from_logits(ops, form, logits, st["input_ids"], st["positions"], st["context_lens"], st["slot_mapping"], st["block_tables"], 256,
+                                 st["tokens"], st["row_steps"])
         else:
             # the winner sits in a different candidate group per row; losers carry smaller values and other columns
             cand_val.fill_(-1.0)
@@ -95,7 +107,8 @@ def test_device_advance_follows_reference_trajectory(golden, form):
     assert (st["row_steps"] == steps - 1).all()
 
 
-def test_padding_rows_are_left_alone():
+@pytest.mark.parametrize("form", LOGITS_FORMS)
+def test_padding_rows_are_left_alone(form):
     """Graph padding rows (context 0, slot -1) are not advanced and log nothing."""
     from nanovllm_hip import ops
     dev = torch.device("cuda")
@@ -108,13 +121,14 @@ def test_padding_rows_are_left_alone():
     bt = torch.tensor([[1, 2], [0, 0], [1, 0]], dtype=torch.int32, device=dev)
     log = torch.full((2, 3), -7, dtype=torch.int64, device=dev)
     rs = torch.zeros(3, dtype=torch.int64, device=dev)
-    ops.greedy_advance(logits, ids, pos, ctx, slots, bt, 256, log, rs)
+    _advance_from_logits(ops, form, logits, ids, pos, ctx, slots, bt, 256, log, rs)
     torch.cuda.synchronize()
     assert ids.tolist() == [7, 6, 7] and pos.tolist() == [301, 0, 13] and ctx.tolist() == [301, 0, 13]
     assert slots.tolist() == [2 * 256 + 44, -1, 256 + 12] and rs.tolist() == [1, 0, 1] and log[0].tolist() == [7, -7, 7]
 
 
-@pytest.mark.parametrize("n", [8, 1000, 151936, 4099])
+# 5: the n % 8 tail alone, no 16-byte chunk; 8200: one full sweep of the 1024 threads plus one chunk
+@pytest.mark.parametrize("n", [8, 1000, 151936, 4099, 5, 8200])
 def test_argmax_edge_rows_follow_torch(n):
     """a row of -inf or NaN logits must still give a VALID index (torch.argmax: NaN counts as the maximum, ties ->
     lowest index), never the kernel's internal sentinel."""
@@ -134,6 +148,10 @@ def test_argmax_edge_rows_follow_torch(n):
     ref = torch.argmax(x.float(), dim=-1)
     torch.cuda.synchronize()
     assert got.tolist() == ref.tolist() and int(got.min()) >= 0 and int(got.max()) < n
+    # the same rows at temperature 0 through the sampling kernels, plain and truncated: one arg-max, three kernels
+    cold = (torch.zeros(6, device=dev), torch.arange(6, dtype=torch.int32, device=dev), torch.zeros(6, dtype=torch.int64, device=dev), 3)
+    assert ops.sample_rows(x, *cold).tolist() == ref.tolist()
+    assert ops.sample_rows(x, *cold, top_k=torch.ones(6, dtype=torch.int32, device=dev)).tolist() == ref.tolist()
 
 
 def test_greedy_advance_survives_degenerate_logits_and_candidates():

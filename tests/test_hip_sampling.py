@@ -69,7 +69,8 @@ def test_noise_matches_float64(seed, key, step):
         assert np.abs(g[:4] + np.log(-np.log(((bits >> U(9)).astype(np.float64) + 0.5) * 2.0 ** -23))).max() <= 2.0 ** -10
 
 
-@pytest.mark.parametrize("m,n,lseed,seed", [(3, 1003, 1, 11), (64, 151936, 2, (1 << 33) + 5)])
+# n = 5: the n % 8 tail alone, no 16-byte chunk; n = 8200: one full sweep of the 1024 threads plus one chunk
+@pytest.mark.parametrize("m,n,lseed,seed", [(3, 1003, 1, 11), (64, 151936, 2, (1 << 33) + 5), (3, 5, 1, 5), (2, 8200, 1, 3)])
 def test_sample_rows_equals_float64_argmax(m, n, lseed, seed):
     from nanovllm_hip import ops
     dev = torch.device("cuda")

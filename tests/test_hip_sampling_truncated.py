@@ -71,7 +71,7 @@ def run(case, seed, top_ks, top_ps):
 
 @pytest.mark.parametrize("top_p", [1.0, 0.8, 1e-6])
 @pytest.mark.parametrize("top_k", [0, 1, 20, -1])                                       # -1: n itself
-@pytest.mark.parametrize("m,n,lseed,seed", [(5, 1003, 2, 11), (8, 151936, 7, (1 << 33) + 5)])
+@pytest.mark.parametrize("m,n,lseed,seed", [(5, 1003, 2, 11), (8, 151936, 7, (1 << 33) + 5), (3, 5, 1, 7), (2, 8200, 1, 3)])   # 5: the tail alone; 8200: a sweep + one chunk
 def test_grid_equals_float64(m, n, lseed, seed, top_k, top_p):
     from nanovllm_hip import ops
     case = rows_case(m, n, lseed, seed)
@@ -85,7 +85,7 @@ def test_grid_equals_float64(m, n, lseed, seed, top_k, top_p):
     if top_k == 1 or top_p == 1e-6:
         assert (kept[np.array(temps) > 0] == 1).all() and np.array_equal(got, greedy)    # a unique maximum in every row
     if top_k == 20 and top_p == 0.8:
-        assert (got != plain).any()
+        assert (got != plain).any() and (kept[np.array(temps) > 0] > 1).any()            # a cut that is neither everything nor the maximum alone
 
 
 def test_ties_keep_the_whole_class():
