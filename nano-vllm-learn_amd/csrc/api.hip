@@ -602,7 +602,7 @@ int nvh_linear_small_m(void* out, const void* x, const void* w, const void* bias
     if (m == 0) return 0;
     if (dtype != NVH_BF16) { set_error("linear_small_m: dtype %d unsupported (bf16 only)", dtype); return NVH_E_DTYPE; }
     if (!out || !x || !w) { set_error("linear_small_m: null pointer"); return NVH_E_NULL; }
-    if (m < 0 || m > 64 || n <= 0 || k <= 0 || k % 32 || n % 16) { set_error("linear_small_m: m=%d (<=64) n=%d (%%16) k=%d (%%32)", m, n, k); return NVH_E_SHAPE; }
+    if (m < 0 || m > 64 || n <= 0 || k <= 0 || k % 64 || n % 16) { set_error("linear_small_m: m=%d (<=64) n=%d (%%16) k=%d (%%64)", m, n, k); return NVH_E_SHAPE; }
     if (silu_inter && (silu_inter * 2 != n || silu_inter % 16 || bias)) { set_error("linear_small_m: silu mode needs n == 2*inter, inter %% 16 == 0, no bias"); return NVH_E_SHAPE; }
     const int out_cols = silu_inter ? silu_inter : n;
     if (x_row_stride % 8 || x_row_stride < k || out_row_stride < out_cols) { set_error("linear_small_m: bad row strides"); return NVH_E_STRIDE; }

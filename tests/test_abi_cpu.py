@@ -86,6 +86,10 @@ def test_argument_validation_without_gpu(lib):
     assert lib.nvh_qkv_rope_attend_status(None, None) == -5
     assert lib.nvh_bf16_rows_to_f16(p, p, 4, 100, 128, 128, None) == -2 and lib.nvh_bf16_rows_to_f16(p, p, 4, 128, 100, 128, None) == -3
     assert lib.nvh_bf16_rows_to_f16(None, None, 0, 128, 128, 128, None) == 0
+    # the streaming linear layer takes K in whole 128-byte weight lines (k % 64), and says so under its own name
+    assert lib.nvh_linear_small_m(p, p, p, None, 4, 16, 96, 0, 96, 16, 0, None) == _E_SHAPE
+    assert b"linear_small_m:" in lib.nvh_last_error() and b"%64" in lib.nvh_last_error()
+    assert lib.nvh_linear_small_m(p, p, p, None, 4, 16, 32, 0, 32, 16, 0, None) == _E_SHAPE
     # prefill with P V on the fp16 pipe: scratch size is a pure function of the shapes; argument errors before any stream operation
     assert lib.nvh_prefill_pv16_scratch_bytes(100, 2, 64) == 256 + 100 * 2 * 64 * 2 and lib.nvh_prefill_pv16_scratch_bytes(0, 2, 64) == 0
     pv = (p, p, p, p, p, p, 2, 1024, 1024, 2048, 14, 2, 64, 896, 128, 128, 0.125, 0, 0)
