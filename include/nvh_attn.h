@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NVH_VERSION 209          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk; 208: nvh_sample_rows / nvh_sample_advance / nvh_gumbel_noise, nvh_linear_desc.sample_*; 209: nvh_sample_rows_truncated / nvh_sample_advance_truncated */
+#define NVH_VERSION 210          /* major*100 + minor; 201: nvh_allreduce_status; 202: nvh_linear_desc.prefetch; 203: NVH_DECODE_CHUNKED_P256; 204: nvh_qkv_rope_attend; 205: nvh_prefill_varlen_pv16; 206: nvh_plan_prefill / nvh_plan_decode; 207: nvh_prefill_varlen_splitk; 208: nvh_sample_rows / nvh_sample_advance / nvh_gumbel_noise, nvh_linear_desc.sample_*; 209: nvh_sample_rows_truncated / nvh_sample_advance_truncated; 210: nvh_linear_small_m[_ex] take m <= 256 */
 
 /* dtype codes */
 #define NVH_BF16 0
@@ -365,8 +365,12 @@ int nvh_sample_advance_truncated(const void* logits, int n_rows, int n, int64_t 
                                  const int32_t* top_ks, const float* top_ps, uint64_t seed, int dtype, void* stream);
 
 /*
- * Engine widening: weight-streaming linear layer for decode-sized batches, out = x . W^T (+ bias), m <= 64 rows.
+ * Engine widening: weight-streaming linear layer for decode-sized batches, out = x . W^T (+ bias), m <= 256 rows.
  * Replaces F.linear in nanovllm/layers/linear.py:55-190 at decode (the hipBLASLt path stays for larger m).
+ * Up to 64 rows the waves of a workgroup split K (csrc/linear_stream.hip); 65..256 rows run csrc/linear_rows.hip, whose waves
+ * split the rows.  That kernel has no K-loop fallback: where nvh_linear_small_m_workspace(m, n, k, epilogue) > 0 (k > 1024, or
+ * k >= 512 under a narrow n) the call needs that workspace, so nvh_linear_small_m itself (which binds none) returns NVH_E_SHAPE
+ * there; use nvh_linear_small_m_ex.
  *   x [m, k] bf16 (row stride in elements); w [n, k] bf16 contiguous (nn.Linear layout); bias [n] bf16 or NULL
  *   silu_inter == 0 : out [m, n] = x w^T + bias
  *   silu_inter  > 0 : n == 2*silu_inter, rows [0, inter) of w are gate_proj and [inter, 2*inter) up_proj
@@ -391,6 +395,9 @@ int nvh_linear_small_m(void* out, const void* x, const void* w, const void* bias
  *            NVH_EPI_ROPE_STORE    n == (h + 2*kvh) * hd (fused qkv projection, models/qwen3.py:104-106): + bias, neox RoPE on
  *                                  the q and k heads, q -> out [m, h*hd]; k and v rows -> k_cache / v_cache at slot_mapping[row]
  *                                  (slot < 0: skipped).  Same arithmetic and rounding points as nvh_rope_store; no q/k norm.
+ * m > 64 (up to 256): every epilogue, x_packed / out_packed and norm_folded as below 65 rows; norm_weight (the exact-norm
+ * prologue), the candidate_* and the sample_* fields are served up to 64 rows only and return NVH_E_SHAPE above (write the logits
+ * and use nvh_greedy_advance / nvh_sample_advance); the prefetch hint is ignored.
  */
 #define NVH_EPI_NONE          0
 #define NVH_EPI_SILU_MUL      1
@@ -419,7 +426,8 @@ typedef struct nvh_linear_desc {
                                        ([ceil(m/16)][cols/32][64][8], cols = n, or silu_inter for SILU_MUL); `out` may then be
                                        NULL for NONE / SILU_MUL */
     void* workspace;                /* NULL or nvh_linear_small_m_workspace() bytes, ZERO-FILLED once by the caller (the
-                                       kernel leaves its tickets zero); needed when k > 1024: K is then split over
+                                       kernel leaves its tickets zero); needed when k > 1024 (m > 64: whenever
+                                       nvh_linear_small_m_workspace() > 0): K is then split over
                                        workgroups and the last-arriving one sums the partials in a fixed order */
     size_t workspace_bytes;
     /* greedy candidates (NONE epilogue, k <= 1024): every workgroup also writes, per row, the largest bf16 output among its
@@ -469,7 +477,7 @@ int nvh_linear_small_m_candidate_groups(int n, int k);      /* candidate records
  * Three forms were built and measured on MI355X (profiles/r03_qkv_attend_*); nvh_qkv_rope_attend runs the winner,
  * nvh_qkv_rope_attend_variant reaches all of them (tests and A/B):
  *   mode 1  TWO launches (the projection, then the attention call).  The winner at every shape tried; mode 0 = this.
- *   mode 2  ONE launch (csrc/qkv_attend.hip): producer workgroups compute the projection's tiles and publish q and the new K/V rows
+ *   mode 2  ONE launch (csrc/qkv_attend.hip; m <= 64 — nvh_qkv_rope_attend itself serves m <= 256 as two launches): producer workgroups compute the projection's tiles and publish q and the new K/V rows
  *           write-through; the attention workgroups start their K/V stream with the launch and wait (bounded) only for those.  Needs
  *           hd == 64, k <= 1024 (no split-K), x_packed, norm_folded, h / kvh <= 16, kvh <= 15 and a grid of at most two workgroups
  *           per CU (all resident: consumers wait for producers) on a device this stream has to itself; NVH_E_SHAPE otherwise.

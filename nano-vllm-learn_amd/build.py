@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "nanovllm_hip", "lib")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libnvh_attn.so")
-SOURCES = ["api.hip", "store_kvcache.hip", "paged_decode.hip", "prefill_mfma.hip", "rope_store.hip", "layer_ops.hip", "skinny_gemm.hip", "linear_stream.hip", "allreduce_oneshot.hip", "qkv_attend.hip", "sample.hip", "sample_truncated.hip"]
+SOURCES = ["api.hip", "store_kvcache.hip", "paged_decode.hip", "prefill_mfma.hip", "rope_store.hip", "layer_ops.hip", "skinny_gemm.hip", "linear_stream.hip", "linear_rows.hip", "allreduce_oneshot.hip", "qkv_attend.hip", "sample.hip", "sample_truncated.hip"]
 HEADERS = ["common.h", "kernels.h", "plan.h", "sample_noise.h", "token_choice.h", "handoff.h", "decode_chunked.h", "prefill_splitk.h", os.path.join("..", "..", "include", "nvh_attn.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA results stay in the architectural VGPRs.  By default hipcc parks accumulators in the AGPR file
@@ -32,7 +32,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
          "-Wall", "-Wno-unused-function", "-Wno-unused-command-line-argument"]
 # rope_store.hip must round RoPE's products and sums separately (bit parity with the reference's elementwise fp32 ops);
 # HIP's default backend contraction ignores the source pragma, so that file is built with contraction off.
-FILE_FLAGS = {"rope_store.hip": ["-ffp-contract=off"], "skinny_gemm.hip": ["-ffp-contract=off"], "linear_stream.hip": ["-ffp-contract=off"]}   # its RoPE epilogue too
+FILE_FLAGS = {"rope_store.hip": ["-ffp-contract=off"], "skinny_gemm.hip": ["-ffp-contract=off"], "linear_stream.hip": ["-ffp-contract=off"], "linear_rows.hip": ["-ffp-contract=off"]}   # its RoPE epilogue too
 
 
 def _digest():

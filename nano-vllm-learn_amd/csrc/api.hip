@@ -602,7 +602,7 @@ int nvh_linear_small_m(void* out, const void* x, const void* w, const void* bias
     if (m == 0) return 0;
     if (dtype != NVH_BF16) { set_error("linear_small_m: dtype %d unsupported (bf16 only)", dtype); return NVH_E_DTYPE; }
     if (!out || !x || !w) { set_error("linear_small_m: null pointer"); return NVH_E_NULL; }
-    if (m < 0 || m > 64 || n <= 0 || k <= 0 || k % 64 || n % 16) { set_error("linear_small_m: m=%d (<=64) n=%d (%%16) k=%d (%%64)", m, n, k); return NVH_E_SHAPE; }
+    if (m < 0 || m > 256 || n <= 0 || k <= 0 || k % 64 || n % 16) { set_error("linear_small_m: m=%d (<=256) n=%d (%%16) k=%d (%%64)", m, n, k); return NVH_E_SHAPE; }
     if (silu_inter && (silu_inter * 2 != n || silu_inter % 16 || bias)) { set_error("linear_small_m: silu mode needs n == 2*inter, inter %% 16 == 0, no bias"); return NVH_E_SHAPE; }
     const int out_cols = silu_inter ? silu_inter : n;
     if (x_row_stride % 8 || x_row_stride < k || out_row_stride < out_cols) { set_error("linear_small_m: bad row strides"); return NVH_E_STRIDE; }
@@ -626,8 +626,8 @@ static int linear_args(LinearArgs& a, const nvh_linear_desc* d, int dtype) {
         return NVH_E_NULL;
     }
     if ((!d->out && !out_optional) || !d->x || !d->w) { set_error("linear_small_m_ex: null pointer"); return NVH_E_NULL; }
-    if (d->m < 0 || d->m > 64 || d->n <= 0 || d->k <= 0 || d->k % 64 || d->n % 16) {
-        set_error("linear_small_m_ex: m=%d (<=64) n=%d (%%16) k=%d (%%64)", d->m, d->n, d->k);
+    if (d->m < 0 || d->m > 256 || d->n <= 0 || d->k <= 0 || d->k % 64 || d->n % 16) {
+        set_error("linear_small_m_ex: m=%d (<=256) n=%d (%%16) k=%d (%%64)", d->m, d->n, d->k);
         return NVH_E_SHAPE;
     }
     int out_cols = d->n;
@@ -690,6 +690,7 @@ int nvh_linear_small_m_ex(const nvh_linear_desc* d, int dtype, void* stream) {
     LinearArgs a;
     const int rca = linear_args(a, d, dtype);
     if (rca) return rca > 0 ? 0 : rca;
+    if (a.M > 64) return launch_linear_rows(a, (hipStream_t)stream);      // 65..256 rows: linear_rows.hip, or NVH_E_SHAPE with the reason
     const int rc = launch_linear_stream(a, (hipStream_t)stream);
     if (rc != -100) return rc;
     if (d->x_packed || d->out_packed || d->candidate_val) {
@@ -720,7 +721,7 @@ static int qkv_rope_attend_impl(int mode, uint32_t spin_limit, int missing_produ
     if (rc) return rc > 0 ? 0 : rc;
     const DecodePlan one = qkv_attend_plan(p);
     const bool can = qkv_attend_supported(l, d, one, device_cus());
-    if (mode == 2 && !can) { set_error("qkv_rope_attend: this shape cannot run as one launch (hd 64, k <= 1024, packed x, folded norm, grid <= 2 x CUs)"); return NVH_E_SHAPE; }
+    if (mode == 2 && !can) { set_error("qkv_rope_attend: this shape cannot run as one launch (m=%d <= 64, hd 64, k <= 1024, packed x, folded norm, grid <= 2 x CUs)", qkv->m); return NVH_E_SHAPE; }
     // mode 0 (what nvh_qkv_rope_attend runs) takes the measured winner: TWO launches.  On MI355X the one-launch form loses at every
     // decode shape tried (its K/V stream fills the memory system's queues in front of the very loads the hand-off
     // chain waits for); it stays reachable (mode 2) and under the same parity tests.
@@ -736,7 +737,7 @@ static int qkv_rope_attend_impl(int mode, uint32_t spin_limit, int missing_produ
         l.pf_kv.passes = spin_limit ? (int)spin_limit : 1;            // (A/B: the variant's spin_limit argument carries the number of passes here)
         if (d.block_size % l.pf_kv.pass_tokens) l.pf_kv.k_cache = nullptr;
     }
-    rc = launch_linear_stream(l, (hipStream_t)stream);
+    rc = l.M > 64 ? launch_linear_rows(l, (hipStream_t)stream) : launch_linear_stream(l, (hipStream_t)stream);   // (above 64 rows: always two launches)
     if (rc == -100) {
         if (qkv->x_packed || qkv->out_packed) { set_error("qkv_rope_attend: packed activations need the streaming kernel"); return NVH_E_SHAPE; }
         rc = launch_linear_small_m(l, (hipStream_t)stream);

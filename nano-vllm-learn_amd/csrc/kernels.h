@@ -161,7 +161,10 @@ struct LinearArgs {
 };
 int launch_linear_small_m(const LinearArgs& a, hipStream_t stream);
 int launch_linear_stream(const LinearArgs& a, hipStream_t stream);   // linear_stream.hip; returns -100 when the shape is not its own
-size_t linear_stream_workspace_bytes(int m, int n, int k, int epi);
+size_t linear_stream_workspace_bytes(int m, int n, int k, int epi);   // m > 64: linear_rows_workspace_bytes
+// linear_rows.hip: the same contract for 65 <= M <= 256 rows (waves split the rows; norm_mode 0 / 2, no candidates); NVH_E_SHAPE otherwise
+int launch_linear_rows(const LinearArgs& a, hipStream_t stream);
+size_t linear_rows_workspace_bytes(int m, int n, int k, int epi);
 
 // element (row, col) of an [M, C] activation in MFMA-fragment order (A operand of v_mfma_f32_16x16x32_bf16):
 // [row / 16][col / 32][lane = 16 * ((col / 8) % 4) + row % 16][col % 8]

@@ -724,6 +724,7 @@ int linear_stream_candidate_groups(int n, int k) {
 // counters [tiles], ONE PER 128-BYTE LINE (the memory side executes the adds on one line one after the other: dense tickets made every
 // tile's last arriver queue behind its neighbours' adds), then partial records [tiles][ksplit][NB*MT*256 + MT*16] fp32; 0 when K needs no split
 size_t linear_stream_workspace_bytes(int m, int n, int k, int epi) {
+    if (m > 64) return linear_rows_workspace_bytes(m, n, k, epi);      // the row-split kernel's own records (linear_rows.hip)
     const int pieces = k / 64, ksplit = (pieces + SW * PMAX - 1) / (SW * PMAX);
     if (ksplit <= 1) return 0;
     const int nb = (epi == EPI_SILU || epi == EPI_ROPE) ? 2 : 1, mt = (m + 15) / 16;

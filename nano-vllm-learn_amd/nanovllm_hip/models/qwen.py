@@ -135,10 +135,16 @@ class RMSNorm(nn.Module):
         return y if residual is None else (y, residual)
 
 
+# Rows up to which the model takes the HIP GEMMs and the fused decode layer.  The kernels serve 256 rows (ops.LINEAR_SMALL_M_MAX), but on
+# MI355X the row-split kernel wins against the vendor GEMM + unfused layer only up to 128 rows (Qwen2-0.5B decode step: 71.5k vs 70.6k
+# tok/s at 128 rows, 86.3k vs 111.4k at 256), so 129..256 rows stay on the vendor path: all five projections.
+_HIP_LINEAR_ROWS = 128
+
+
 def linear(x, weight, bias=None):
-    """F.linear; decode-sized batches on the GPU take the weight-streaming HIP kernel (ops.linear_small_m), anything
-    else (prefill, CPU tests) goes to the vendor GEMM."""
-    if x.is_cuda and x.dtype == torch.bfloat16 and x.numel() // x.shape[-1] <= 64 and x.shape[-1] % 64 == 0 and weight.shape[0] % 16 == 0:
+    """F.linear; decode-sized batches on the GPU (up to _HIP_LINEAR_ROWS rows) take the weight-streaming HIP kernels (ops.linear_small_m),
+    anything else (prefill, CPU tests) goes to the vendor GEMM."""
+    if x.is_cuda and x.dtype == torch.bfloat16 and x.numel() // x.shape[-1] <= _HIP_LINEAR_ROWS and x.shape[-1] % 64 == 0 and weight.shape[0] % 16 == 0:
         from .. import ops
         return ops.linear_small_m(x, weight, bias)
     return F.linear(x, weight, bias)
@@ -245,7 +251,7 @@ class QwenMLP(nn.Module):
 
     def forward(self, x):
         w = self.gate_up_proj.weight
-        if x.is_cuda and x.dtype == torch.bfloat16 and x.numel() // x.shape[-1] <= 64 and x.shape[-1] % 64 == 0 and w.shape[0] % 32 == 0:
+        if x.is_cuda and x.dtype == torch.bfloat16 and x.numel() // x.shape[-1] <= _HIP_LINEAR_ROWS and x.shape[-1] % 64 == 0 and w.shape[0] % 32 == 0:
             from .. import ops
             act = ops.linear_small_m(x, w, silu_mul=True)         # gate_up projection + SiLU*mul in one launch
         else:
@@ -304,10 +310,12 @@ class PackedResidual:
 
 
 def _fused_decode_ok(cfg, x):
-    """The 5-launch decoder layer (6 with Qwen3's q/k-norm) applies to single-GPU decode batches of at most 64 rows."""
+    """The 5-launch decoder layer (6 with Qwen3's q/k-norm) applies to decode batches of at most _HIP_LINEAR_ROWS rows on a single GPU
+    (above 64 rows: csrc/linear_rows.hip) and of at most 64 rows under tensor parallelism (the one-shot all-reduce staging is
+    sized for 64 rows)."""
     from ..utils.context import get_context
     ctx = get_context()
-    return (FUSED_DECODE and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] <= 64 and not ctx.is_prefill
+    return (FUSED_DECODE and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] <= (_HIP_LINEAR_ROWS if _tp()[1] == 1 else 64) and not ctx.is_prefill
             and ctx.context_lens is not None and ctx.slot_mapping is not None and cfg.attn_backend == "hip")
 
 
@@ -477,7 +485,7 @@ class QwenForCausalLM(nn.Module):
         (val [groups, stride] float32, idx int32, groups) for ops.greedy_advance_candidates, or None when this path does not
         apply (then use compute_logits).  sampling = (temperatures, row_keys, steps, seed): the candidates of the perturbed
         scores (ops.fused_linear), i.e. the same call then SAMPLES."""
-        if not isinstance(hidden_states, PackedResidual):
+        if not isinstance(hidden_states, PackedResidual) or hidden_states.shape[0] > 64:     # above 64 rows the LM head writes its logits
             return None
         packed = hidden_states.packed
         from .. import ops

@@ -347,18 +347,25 @@ def silu_mul(gate_up):
     return out.view(*gate_up.shape[:-1], inter)
 
 
-LINEAR_SMALL_M_MAX = 64
+LINEAR_SMALL_M_MAX = 256         # up to 64 rows: csrc/linear_stream.hip (waves split K); 65..256: csrc/linear_rows.hip (waves split the rows)
 
 
 def linear_small_m(x, weight, bias=None, silu_mul=False):
-    """F.linear(x, weight, bias) for at most 64 rows, streaming `weight` [N, K] once; with silu_mul=True `weight` is the
-    merged gate_up projection and the result is SiLU(x gate^T) * (x up^T) (projection + activation.py:11-14 in one launch)."""
+    """F.linear(x, weight, bias) for at most 256 rows, streaming `weight` [N, K] once; with silu_mul=True `weight` is the
+    merged gate_up projection and the result is SiLU(x gate^T) * (x up^T) (projection + activation.py:11-14 in one launch).
+    Above 64 rows a long K (> 1024, or >= 512 under a narrow N) is split over workgroups: the per-device zero-filled workspace
+    of reserve_workspace(kind="linear_rows") is bound then (one such call at a time per device)."""
     _require_gpu_bf16(x=x, weight=weight)
     k = x.shape[-1]
     x2 = x.view(-1, k)
     n = weight.shape[0]
     assert x2.shape[0] <= LINEAR_SMALL_M_MAX and x2.stride(1) == 1 and weight.is_contiguous() and weight.shape[1] == k
     inter = n // 2 if silu_mul else 0
+    if x2.shape[0] > 64:                                   # the row-split kernel has no K loop: bind the hand-off workspace where K is split
+        epi = "silu_mul" if silu_mul else "none"
+        need = linear_workspace_bytes(x2.shape[0], n, k, epi)
+        ws = reserve_workspace(x.device, need, "linear_rows") if need else None
+        return fused_linear(x2, weight, bias=bias, epilogue=epi, workspace=ws).view(*x.shape[:-1], inter if silu_mul else n)
     out = torch.empty((x2.shape[0], inter if silu_mul else n), dtype=torch.bfloat16, device=x.device)
     if bias is not None:
         _require_gpu_bf16(bias=bias)
@@ -395,7 +402,7 @@ _EPI_CODES = {"none": _lib.EPI_NONE, "silu_mul": _lib.EPI_SILU_MUL, "residual_ad
 
 def fused_linear(x, weight, *, bias=None, norm_weight=None, norm_eps=1e-6, norm_folded=False, epilogue="none", out=None, rope=None,
                  x_packed_rows=None, out_packed=None, workspace=None, want_out=True, candidates=None, prefetch=None, sampling=None):
-    """nvh_linear_small_m_ex: x [M<=64, K] . weight[N, K]^T with an optional RMSNorm prologue and one of the epilogues
+    """nvh_linear_small_m_ex: x [M<=256, K] . weight[N, K]^T with an optional RMSNorm prologue and one of the epilogues
     "none" (+bias) | "silu_mul" | "residual_add" (out = the residual stream, updated in place) | "rope_store"
     (rope = dict(positions, cos_sin, k_cache, v_cache, slot_mapping, num_heads, num_kv_heads, head_dim); returns q [M, H*D]).
     Streaming form: x_packed_rows = M when `x` is a flat fragment-order buffer (pack_rows); out_packed = a flat bf16 buffer
@@ -407,7 +414,10 @@ def fused_linear(x, weight, *, bias=None, norm_weight=None, norm_eps=1e-6, norm_
     prefetch = a contiguous CUDA tensor the NEXT launch will stream (the following projection's weights): the CUs this launch
     leaves idle read it into the caches first (a hint; results do not depend on it).
     sampling = (temperatures float32 [M], row_keys uint32 [M], steps int64 [M], seed) with candidates only: the candidates are taken
-    over the perturbed scores of sample_rows, so that greedy_advance_candidates picks the SAMPLED token (rows with T <= 0: greedy)."""
+    over the perturbed scores of sample_rows, so that greedy_advance_candidates picks the SAMPLED token (rows with T <= 0: greedy).
+    65 <= M <= 256 rows run csrc/linear_rows.hip: the same epilogues and packed forms with norm_folded or no norm; there K is
+    split whenever linear_workspace_bytes() > 0 (the workspace is then required), and norm_weight, candidates and sampling are
+    refused (NVH_E_SHAPE): write the logits and use greedy_advance / sample_advance."""
     d, out = _linear_desc(x, weight, bias=bias, norm_weight=norm_weight, norm_eps=norm_eps, norm_folded=norm_folded, epilogue=epilogue, out=out,
                           rope=rope, x_packed_rows=x_packed_rows, out_packed=out_packed, workspace=workspace, want_out=want_out,
                           candidates=candidates, prefetch=prefetch, sampling=sampling)
